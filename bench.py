@@ -19,6 +19,19 @@ serialization.  `engine_tokens_per_s` (engine-side count over the same
 window) is reported alongside so the gateway overhead is quantified.
 `ms_per_step` is MAX over workers of elapsed/K.
 
+A plain run does only what that figure needs: start the host and its
+workers, ramp the streams up (the workers prefill every stream and then
+park decoding, so each run enters the window with the same sequence
+lengths), W warmup + K timed steps, print the result line.  ``--full``
+adds the measurements that take requests of their own (today: the p50
+TTFT probe, `ttft_ms_p50`; it is null in a plain run).
+
+``--dump-outputs DIR`` writes what the last timed step handed to its
+callers as ``DIR/tokens.npy`` (float32): one sampled token id per running
+stream, workers in socket order, streams in engine batch order.  Prompts,
+seeds and the step sequence are fixed by the arguments, so two builds can
+be compared output for output.
+
 ``--engine-direct`` keeps the round-1 in-process engine loop (used for
 rocprof profiling, kernel work, and as the overhead cross-check).
 
@@ -42,10 +55,11 @@ import threading
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
+T_START = time.time()
 
 
 def log(msg):
-    print(f"[bench] {msg}", flush=True)
+    print(f"[bench +{time.time() - T_START:.1f}s] {msg}", flush=True)
 
 
 # --------------------------------------------------------------- helpers
@@ -74,9 +88,18 @@ def ensure_host_binary():
     if not os.path.exists(bin_path):
         log("building host binary (make -C host)")
         subprocess.run(["make", "-C", os.path.join(REPO, "host"),
-                        f"-j{os.cpu_count() or 8}"], check=True,
+                        f"-j{min(os.cpu_count() or 8, 16)}"], check=True,
                        stdout=subprocess.DEVNULL)
     return bin_path
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one float32 .npy per named output."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, values in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.asarray(values, dtype=np.float32))
 
 
 def _http_json(method, url, body=None, timeout=30):
@@ -245,7 +268,7 @@ def measure_ttft(port, model, prompt_text, iters=10):
 
 # --------------------------------------------------------------- REST mode
 
-def write_config(args, port, sock_prefix, n_workers, on_gpu):
+def write_config(args, port, sock_prefix, n_workers, on_gpu, home):
     worker_lines = [
         f"        max_num_seqs: {args.batch}",
         # decode headroom: streams keep generating from admission until
@@ -258,6 +281,12 @@ def write_config(args, port, sock_prefix, n_workers, on_gpu):
         worker_lines.append(f"        count: {n_workers}")
     if args.eager or not on_gpu:
         worker_lines.append("        eager: true")
+    elif not args.full and args.warmup > 0:
+        # only the decode graph of the timed batch size is needed: it is
+        # captured in the first warmup step (with no warmup the capture
+        # would land in the timed steps); --full keeps the start-up
+        # capture of every bucket (the TTFT probe replays prefill graphs)
+        worker_lines.append("        lazy_graphs: true")
     if not on_gpu:
         worker_lines.append('        device: "cpu"')
         worker_lines.append("        num_gpu_blocks: 2048")
@@ -267,7 +296,7 @@ def write_config(args, port, sock_prefix, n_workers, on_gpu):
         worker_lines.append(f'        kv_dtype: "{args.kv_dtype}"')
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-bench"
+  home_dir: "{home}"
 logging:
   default:
     console_level: warn
@@ -296,7 +325,7 @@ modules:
       worker:
 {chr(10).join(worker_lines)}
 """
-    path = f"/tmp/hs-bench-{os.getpid()}.yaml"
+    path = os.path.join(home, "bench.yaml")
     with open(path, "w") as f:
         f.write(cfg)
     return path
@@ -316,7 +345,7 @@ def wait_workers(port, n_workers, timeout=1200):
                 return j
         except Exception:
             pass
-        time.sleep(1.0)
+        time.sleep(0.2)
     raise TimeoutError(f"workers not ready after {timeout}s: {last}")
 
 
@@ -336,17 +365,25 @@ def wait_saturated(port, per_worker, timeout=3600):
                 return j
         except Exception:
             pass
-        time.sleep(1.0)
+        time.sleep(0.1)
     raise TimeoutError("streams never reached steady-state decode")
 
 
-def rest_bench_rank0(args, n_gpus, on_gpu):
+class GpuGuessWrong(Exception):
+    pass
+
+
+def rest_bench_rank0(args, n_gpus, on_gpu, confirm=False):
     _raise_nofile()
     binary = ensure_host_binary()
     port = _free_port()
     sock_prefix = f"/tmp/hs-bench-{os.getpid()}.sock"
     n_workers = 1 if args.tp > 1 else n_gpus
-    cfg_path = write_config(args, port, sock_prefix, n_workers, on_gpu)
+    import shutil
+    import tempfile
+    home = tempfile.mkdtemp(prefix="hs-bench-")
+    cfg_path = write_config(args, port, sock_prefix, n_workers, on_gpu,
+                            home)
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env["PYTHONPATH"] = REPO + os.pathsep + env.get("PYTHONPATH", "")
@@ -357,6 +394,11 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
                [f"{sock_prefix}.{i}" for i in range(n_workers)])
     try:
         t0 = time.time()
+        log("host started")
+        if confirm:
+            import torch
+            if torch.cuda.is_available() != on_gpu:
+                raise GpuGuessWrong()
         wait_workers(port, n_workers)
         log(f"host + {n_workers} worker(s) ready in {time.time()-t0:.0f}s "
             f"(model={args.model}, tp={args.tp})")
@@ -368,9 +410,21 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
         prompt_text = "".join(
             chr(rng.randint(0x21, 0x7e)) for _ in range(args.prompt_len - 1))
 
-        ttft_p50 = measure_ttft(port, args.model, prompt_text,
-                                iters=args.ttft_iters)
-        log(f"REST TTFT p50 {ttft_p50:.1f} ms (prompt {args.prompt_len})")
+        ttft_p50 = None
+        if args.full:
+            ttft_p50 = measure_ttft(port, args.model, prompt_text,
+                                    iters=args.ttft_iters)
+            log(f"REST TTFT p50 {ttft_p50:.1f} ms "
+                f"(prompt {args.prompt_len})")
+
+        # every stream is prefilled on arrival and then waits for the
+        # timed window, so the window starts from the same sequence
+        # lengths whatever the arrival timing was
+        for sp in sockets:
+            r = _uds_request(sp, {"type": "bench_hold",
+                                  "streams": args.batch}, timeout=30)
+            if not r or r.get("event") != "bench_hold":
+                raise RuntimeError(f"worker refused bench_hold: {r}")
 
         # ---- sustained load: batch streams per worker ----
         total_streams = args.batch * n_workers if args.tp == 1 else args.batch
@@ -407,7 +461,7 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
         while (client.streams_started < total_streams * 0.99
                and time.time() - t0 < 900):
             ramp_progress()
-            time.sleep(0.5)
+            time.sleep(0.1)
         if client.streams_started < total_streams * 0.95:
             raise RuntimeError(
                 f"only {client.streams_started}/{total_streams} streams "
@@ -417,15 +471,18 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
             f"({time.time()-t0:.0f}s ramp, {client.errors} conn errors)")
 
         # ---- timed window: workers step W+K with sync brackets ----
-        start_at = time.time() + 1.0
-        results = []
+        # a fleet needs a common start time far enough ahead for every
+        # worker to have the op; one worker just starts
+        start_at = time.time() + (1.0 if len(sockets) > 1 else 0.1)
+        results = [None] * len(sockets)
         threads = []
-        def run_bench(sp):
-            results.append(_uds_request(sp, {
+        def run_bench(i, sp):
+            results[i] = _uds_request(sp, {
                 "type": "bench", "warmup": args.warmup,
-                "steps": args.steps, "start_at": start_at}))
-        for sp in sockets:
-            th = threading.Thread(target=run_bench, args=(sp,))
+                "steps": args.steps, "start_at": start_at,
+                "last_tokens": bool(args.dump_outputs)})
+        for i, sp in enumerate(sockets):
+            th = threading.Thread(target=run_bench, args=(i, sp))
             th.start()
             threads.append(th)
         for th in threads:
@@ -433,8 +490,11 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
         ok = [r for r in results if r and r.get("event") == "bench_done"]
         if len(ok) != len(sockets):
             raise RuntimeError(f"bench op failed on some workers: {results}")
-        time.sleep(1.0)                     # let in-flight SSE drain
+        time.sleep(0.25)                    # let in-flight SSE drain
         client.stop()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {
+                "tokens": [t for r in ok for t in r["last_tokens"]]})
 
         if "ms_engine" in ok[0]:
             log("worker step breakdown: "
@@ -464,12 +524,9 @@ def rest_bench_rank0(args, n_gpus, on_gpu):
             host.wait(timeout=30)
         except subprocess.TimeoutExpired:
             host.kill()
+        log("host stopped")
         logf.close()
-        for p in [cfg_path]:
-            try:
-                os.unlink(p)
-            except OSError:
-                pass
+        shutil.rmtree(home, ignore_errors=True)
 
 
 # --------------------------------------------------- engine-direct mode
@@ -511,20 +568,24 @@ def engine_direct(args, rank, world, on_gpu):
     g = _t.Generator().manual_seed(7)
     vocab = cfg.spec().vocab_size
 
-    def mk_prompt(n):
-        return _t.randint(0, vocab, (n,), generator=g).tolist()
+    def mk_prompt(n, gen=g):
+        return _t.randint(0, vocab, (n,), generator=gen).tolist()
 
-    ttfts = []
-    for _ in range(5):
-        eng.add_request(mk_prompt(args.prompt_len),
-                        SamplingParams(temperature=0.0, max_tokens=1))
-        t = time.monotonic()
-        while eng.has_work():
-            eng.step()
-        if on_gpu:
-            torch.cuda.synchronize()
-        ttfts.append((time.monotonic() - t) * 1000)
-    ttft_p50 = statistics.median(ttfts)
+    ttft_p50 = None
+    if args.full:
+        # own generator: the timed batch gets the same prompts either way
+        g_ttft = _t.Generator().manual_seed(11)
+        ttfts = []
+        for _ in range(5):
+            eng.add_request(mk_prompt(args.prompt_len, g_ttft),
+                            SamplingParams(temperature=0.0, max_tokens=1))
+            t = time.monotonic()
+            while eng.has_work():
+                eng.step()
+            if on_gpu:
+                torch.cuda.synchronize()
+            ttfts.append((time.monotonic() - t) * 1000)
+        ttft_p50 = statistics.median(ttfts)
 
     sp = SamplingParams(temperature=0.0, max_tokens=10 ** 9)
     for _ in range(args.batch):
@@ -543,8 +604,10 @@ def engine_direct(args, rank, world, on_gpu):
         dist.barrier()
     t0 = time.monotonic()
     produced = 0
+    last = []
     for _ in range(args.steps):
-        produced += len(eng.step())
+        last = eng.step()
+        produced += len(last)
     if on_gpu:
         torch.cuda.synchronize()
     if world > 1:
@@ -559,10 +622,14 @@ def engine_direct(args, rank, world, on_gpu):
         produced = int(p[0])
     if world > 1:
         dist.destroy_process_group()
+    if args.dump_outputs and rank == 0:
+        # rank 0's engine (at tp>1 every rank samples the same tokens)
+        dump_outputs(args.dump_outputs,
+                     {"tokens": [o.token_id for o in last]})
     return {
         "value": round(produced / elapsed, 2),
         "ms_per_step": round(elapsed / args.steps * 1000, 3),
-        "ttft_ms_p50": round(ttft_p50, 2),
+        "ttft_ms_p50": round(ttft_p50, 2) if ttft_p50 else None,
         "global_batch": args.batch * (1 if tp > 1 else world),
     }
 
@@ -593,20 +660,40 @@ def main():
     ap.add_argument("--kv-dtype", default="bfloat16",
                     choices=["bfloat16", "fp8"])
     ap.add_argument("--device", default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements that take requests "
+                         "of their own (p50 TTFT probe)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as "
+                         "DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
-    import torch
-    import torch.distributed as dist
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    on_gpu = torch.cuda.is_available() and args.device != "cpu"
+    # the single-process REST run needs torch only to learn whether a GPU
+    # is there: guess from the device node, start the host, and confirm
+    # with torch while the workers load
+    lazy = (not args.engine_direct and world == 1
+            and args.device != "cpu")
+    if lazy:
+        on_gpu = os.access("/dev/kfd", os.R_OK | os.W_OK)
+    else:
+        import torch
+        import torch.distributed as dist
+        on_gpu = torch.cuda.is_available() and args.device != "cpu"
     n_gpus = world if world > 1 else args.gpus
 
-    if not on_gpu and args.model == "llama3-8b" and not args.engine_direct:
-        # CPU dev-run: the 8B model at fp32 on CPU is not a dev loop
-        args.model = "tiny-llama"
-        args.batch = min(args.batch, 8)
-        args.prompt_len = min(args.prompt_len, 64)
+    def cpu_dev_run(a, gpu):
+        if not gpu and a.model == "llama3-8b" and not a.engine_direct:
+            # CPU dev-run: the 8B model at fp32 on CPU is not a dev loop
+            a.model = "tiny-llama"
+            a.batch = min(a.batch, 8)
+            a.prompt_len = min(a.prompt_len, 64)
+        return a
+
+    import copy
+    args_in = copy.copy(args)
+    cpu_dev_run(args, on_gpu)
 
     if args.engine_direct:
         res = engine_direct(args, rank, world, on_gpu)
@@ -619,7 +706,14 @@ def main():
             dist.init_process_group("gloo",
                                     timeout=timedelta(seconds=7200))
         if rank == 0:
-            res = rest_bench_rank0(args, n_gpus, on_gpu)
+            try:
+                res = rest_bench_rank0(args, n_gpus, on_gpu, confirm=lazy)
+            except GpuGuessWrong:
+                on_gpu = not on_gpu
+                log(f"device-node guess was wrong; restarting with "
+                    f"on_gpu={on_gpu}")
+                args = cpu_dev_run(args_in, on_gpu)
+                res = rest_bench_rank0(args, n_gpus, on_gpu)
         else:
             res = None
         if world > 1:

@@ -574,6 +574,8 @@ void LlmGatewayModule::spawn_one(Worker& wk) {
       }
       if (worker_cfg_.at("eager").as_bool(false))
         args.push_back("--eager");
+      if (worker_cfg_.at("lazy_graphs").as_bool(false))
+        args.push_back("--lazy-graphs");
       if (worker_cfg_.contains("device")) {
         args.push_back("--device");
         args.push_back(worker_cfg_.at("device").as_string());

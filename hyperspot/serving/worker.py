@@ -9,6 +9,9 @@ round-trips).  Speaks newline-delimited JSON over a Unix socket:
   <- {"event":"done","id":r,"finish_reason":f,"usage":{...}}
   -> {"type":"abort","id":r}
   -> {"type":"info"}           <- {"event":"info","ready":true,...}
+  -> {"type":"bench_hold","streams":n}   (bench.py: prefill n streams in
+                                          full-budget steps, park decode)
+  -> {"type":"bench","warmup":w,"steps":k,...}   <- {"event":"bench_done"}
 
 One stepping thread drives the continuous-batching engine; connection
 threads only enqueue requests and drain per-request token queues, so the
@@ -60,8 +63,12 @@ class WorkerState:
         self.started = {}                     # rid -> prompt_len
         self.pending_ops = []                 # ops since last broadcast
         self.stop = False
-        self.bench_req = None                 # (warmup, steps, start_at)
+        self.bench_req = None     # (warmup, steps, start_at, want_tokens)
         self.bench_result = queue.Queue()
+        self.hold_decode = False              # bench: park until the window
+        self.hold_streams = 0                 # bench: streams to wait for
+        self._last_arrival = 0.0
+        self._last_outputs = []               # StepOutputs of the last step
         self.pending_exec = []                # (kind, arg, reply_q)
         self.mux_of = {}                      # rid -> MuxChannel
         self.submit_mu = threading.Lock()
@@ -198,12 +205,37 @@ class WorkerState:
         with self.submit_mu:
             subs = self.pending_submits
             self.pending_submits = []
+        self._last_arrival = time.time()
         for rid, prompt_ids, sampling, mux in subs:
             self.mux_of[rid] = mux
             self.engine.add_request(prompt_ids, sampling, request_id=rid)
             if self.tp > 1:
                 self.pending_ops.append(
                     ("add", rid, prompt_ids, sampling.__dict__.copy()))
+
+    def _ramp_incomplete(self):
+        """True while the next prefill step would depend on arrival
+        timing: fewer streams than bench_hold announced have come in and
+        the queue cannot yet fill a whole step's token budget.  (2 s of
+        silence gives up, so a short ramp degrades to arrival-order
+        batches, not a hang.)"""
+        eng = self.engine
+        if eng.num_running + eng.num_waiting >= self.hold_streams:
+            self.hold_streams = 0
+            return False
+        queued = sum(r.num_prompt_tokens - r.num_computed_tokens
+                     for r in eng.scheduler.waiting)
+        if queued >= eng.config.max_num_batched_tokens:
+            return False
+        return time.time() - self._last_arrival < 2.0
+
+    def _only_decode_left(self):
+        """True when the next engine step would be a decode step: no
+        request is waiting, or none of the waiting ones can be admitted."""
+        eng = self.engine
+        return eng.num_running > 0 and (
+            eng.num_waiting == 0
+            or eng.num_running >= eng.config.max_num_seqs)
 
     def _exec(self, kind, arg):
         if kind == "swap":
@@ -255,6 +287,14 @@ class WorkerState:
                         q.put(e)
                 self._drain_submits_locked()
                 if not self.engine.has_work() and not self.pending_ops:
+                    continue
+                if self.hold_decode and (self._ramp_incomplete()
+                                         or self._only_decode_left()):
+                    # bench ramp: a prefill step runs only with a whole
+                    # token budget queued (same prefill batches on
+                    # every run), and decoding resumes with the bench
+                    # op (same sequence lengths at the timed window)
+                    self.new_work.wait(timeout=0.02)
                     continue
                 if self.tp > 1:
                     ops = self.pending_ops
@@ -308,6 +348,7 @@ class WorkerState:
         self._bt_lock += t1 - t0
         self._bt_step += t2 - t1
         self._bt_fanout += t3 - t2
+        self._last_outputs = outputs
         return len(outputs)
 
     def _sync(self):
@@ -329,8 +370,9 @@ class WorkerState:
         measured *while serving*, not in isolation.  t0/t1 are epoch
         seconds so the REST client (same box) can count delivered
         tokens inside the same wall-clock window."""
-        warmup, steps, start_at = self.bench_req
+        warmup, steps, start_at, want_tokens = self.bench_req
         self.bench_req = None
+        self.hold_decode = False
         try:
             while time.time() < start_at:       # align fleet windows
                 time.sleep(0.001)
@@ -344,7 +386,14 @@ class WorkerState:
                 produced += self._one_step()
             self._sync()
             t1 = time.time()
+            extra = {}
+            if want_tokens:
+                # what the last timed step handed to the streams, in
+                # engine batch order (= admission order)
+                extra["last_tokens"] = [o.token_id
+                                        for o in self._last_outputs]
             self.bench_result.put({
+                **extra,
                 "event": "bench_done", "t0": t0, "t1": t1,
                 "elapsed": t1 - t0, "produced": produced,
                 "steps": steps, "warmup": warmup,
@@ -604,6 +653,15 @@ def handle_conn(conn: socket.socket, state: WorkerState, model_name: str):
                       "kv_blocks_total": state.engine.runner.num_blocks})
             elif t == "abort":
                 state.abort(msg.get("id", ""))
+            elif t == "bench_hold":
+                # operator-plane op: prefill the announced streams in
+                # full-budget steps and park decoding until the next
+                # "bench" op opens its window
+                with state.new_work:
+                    state.hold_decode = True
+                    state.hold_streams = int(msg.get("streams", 0))
+                    state._last_arrival = time.time() + 30  # first burst
+                send({"event": "bench_hold"})
             elif t == "bench":
                 # operator-plane op: time W warmup + K steps around the
                 # live serving load (bench.py REST-mode contract)
@@ -611,7 +669,8 @@ def handle_conn(conn: socket.socket, state: WorkerState, model_name: str):
                 k_ = int(msg.get("steps", 64))
                 start_at = float(msg.get("start_at", 0.0))
                 with state.new_work:
-                    state.bench_req = (w_, k_, start_at)
+                    state.bench_req = (w_, k_, start_at,
+                                       bool(msg.get("last_tokens")))
                     state.new_work.notify()
                 wait_s = max(0.0, start_at - time.time()) + 600
                 try:
@@ -756,6 +815,9 @@ def main():
     ap.add_argument("--max-model-len", type=int, default=8192)
     ap.add_argument("--num-gpu-blocks", type=int, default=0)
     ap.add_argument("--eager", action="store_true")
+    ap.add_argument("--lazy-graphs", action="store_true",
+                    help="capture each decode/prefill hipGraph at its "
+                         "first use instead of all of them at start-up")
     ap.add_argument("--device", default=None)
     ap.add_argument("--tp", type=int, default=1)
     ap.add_argument("--ep", type=int, default=0,
@@ -803,7 +865,7 @@ def main():
              args.device, rank)
     eng = LLMEngine(cfg, device=args.device,
                     eos_token_id=ByteTokenizer(cfg.spec().vocab_size).eos_token_id)
-    if not cfg.enforce_eager:
+    if not cfg.enforce_eager and not args.lazy_graphs:
         eng.capture_graphs()
     if args.tp > 1 and rank != 0:
         follower_loop(eng)      # blocks until rank 0 broadcasts stop

@@ -15,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_rest_json_line():
     out = subprocess.run(
         [sys.executable, os.path.join(ROOT, "bench.py"),
-         "--steps", "4", "--warmup", "1", "--ttft-iters", "3"],
+         "--steps", "4", "--warmup", "1", "--full", "--ttft-iters", "3"],
         cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -35,6 +35,31 @@ def test_bench_rest_json_line():
                                 "parallelism"}
     # REST-vs-engine overhead is quantified (VERDICT round-1 item 2)
     assert "engine_tokens_per_s" in j and "gateway_overhead_pct" in j
+
+
+def test_bench_plain_run_dumps_repeatable_outputs(tmp_path):
+    """A plain run skips the TTFT probe (it sits behind --full), and
+    --dump-outputs writes the last timed step's token ids as float32,
+    identical from run to run."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        out = subprocess.run(
+            [sys.executable, os.path.join(ROOT, "bench.py"),
+             "--steps", "3", "--warmup", "1",
+             "--dump-outputs", str(tmp_path / name)],
+            cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["ttft_ms_p50"] is None
+        arr = np.load(tmp_path / name / "tokens.npy")
+        assert arr.dtype == np.float32
+        assert arr.shape == (j["config"]["global_batch"],)
+        dumps.append(arr)
+    assert (dumps[0] == dumps[1]).all()
 
 
 def test_bench_rest_two_rank_launch():

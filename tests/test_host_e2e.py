@@ -11,6 +11,7 @@ import json
 import os
 import socket
 import subprocess
+import tempfile
 import time
 import urllib.error
 import urllib.request
@@ -21,6 +22,9 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 BIN = Path(os.environ.get("HS_SERVER_BIN",
                           ROOT / "host" / "build" / "hyperspot-server"))
+# server home dirs live under a directory of this run's own: a fixed /tmp
+# path left behind by another user's run is not writable
+_TMP = tempfile.mkdtemp(prefix="hs-e2e-")
 
 
 def _free_port():
@@ -128,7 +132,7 @@ def server():
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e"
+  home_dir: "{_TMP}/hs-e2e"
 logging:
   default:
     console_level: warn
@@ -315,7 +319,7 @@ def mt_server():
     sock = tempfile.mktemp(suffix=".sock", prefix="hs-mt-")
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-mt"
+  home_dir: "{_TMP}/hs-e2e-mt"
 logging:
   default:
     console_level: warn
@@ -720,7 +724,7 @@ while True:
 """)
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-oop"
+  home_dir: "{_TMP}/hs-e2e-oop"
 logging:
   default:
     console_level: warn
@@ -889,7 +893,7 @@ def licensed_server():
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-lic"
+  home_dir: "{_TMP}/hs-e2e-lic"
 logging:
   default:
     console_level: warn
@@ -999,7 +1003,7 @@ def dp_server():
     sock = tempfile.mktemp(suffix=".sock", prefix="hs-dp-")
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-dp"
+  home_dir: "{_TMP}/hs-e2e-dp"
 logging:
   default:
     console_level: warn
@@ -1197,7 +1201,7 @@ def hooked_server():
     sock = tempfile.mktemp(suffix=".sock", prefix="hs-hook-")
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-hook"
+  home_dir: "{_TMP}/hs-e2e-hook"
 logging:
   default:
     console_level: warn
@@ -1315,7 +1319,7 @@ def timeout_server():
     sock = tempfile.mktemp(suffix=".sock", prefix="hs-to-")
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-to"
+  home_dir: "{_TMP}/hs-e2e-to"
 logging:
   default:
     console_level: warn
@@ -1501,7 +1505,7 @@ def test_rest_serving_with_tp2_worker():
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-tp2"
+  home_dir: "{_TMP}/hs-e2e-tp2"
 logging:
   default:
     console_level: warn
@@ -1558,7 +1562,7 @@ def oop_parser_server(tmp_path_factory):
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-oopfp"
+  home_dir: "{_TMP}/hs-e2e-oopfp"
 logging:
   default:
     console_level: warn
@@ -1911,7 +1915,7 @@ def test_chat_per_tenant_admission_limit(tmp_path):
     cfg_path = Path(tempfile.mktemp(suffix=".yaml"))
     cfg_path.write_text(f"""
 server:
-  home_dir: "/tmp/hs-e2e-adm"
+  home_dir: "{_TMP}/hs-e2e-adm"
 logging:
   default:
     console_level: warn
@@ -1981,7 +1985,7 @@ def test_chat_tenant_budget_exhausted(tmp_path):
     cfg_path = Path(tempfile.mktemp(suffix=".yaml"))
     cfg_path.write_text(f"""
 server:
-  home_dir: "/tmp/hs-e2e-bud"
+  home_dir: "{_TMP}/hs-e2e-bud"
 logging:
   default:
     console_level: warn
@@ -2037,7 +2041,7 @@ def test_hook_response_blocked(tmp_path):
     cfg_path = Path(tempfile.mktemp(suffix=".yaml"))
     cfg_path.write_text(f"""
 server:
-  home_dir: "/tmp/hs-e2e-rhook"
+  home_dir: "{_TMP}/hs-e2e-rhook"
 logging:
   default:
     console_level: warn
@@ -2087,7 +2091,7 @@ def test_job_result_ttl_expires(tmp_path):
     cfg_path = Path(tempfile.mktemp(suffix=".yaml"))
     cfg_path.write_text(f"""
 server:
-  home_dir: "/tmp/hs-e2e-ttl"
+  home_dir: "{_TMP}/hs-e2e-ttl"
 logging:
   default:
     console_level: warn

@@ -17,7 +17,7 @@ from pathlib import Path
 
 import pytest
 
-from tests.test_host_e2e import ServerProc, _free_port, _http
+from tests.test_host_e2e import _TMP, ServerProc, _free_port, _http
 
 BASE = "http://127.0.0.1:{}"
 
@@ -99,7 +99,7 @@ def jwks_env():
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-jwks"
+  home_dir: "{_TMP}/hs-e2e-jwks"
 logging:
   default:
     console_level: warn
@@ -223,7 +223,7 @@ def test_jwks_fetch_retries_transient_5xx():
     cfg_path = Path(tempfile.mktemp(suffix=".yaml"))
     cfg_path.write_text(f"""
 server:
-  home_dir: "/tmp/hs-e2e-jwks-flaky"
+  home_dir: "{_TMP}/hs-e2e-jwks-flaky"
 logging:
   default:
     console_level: warn

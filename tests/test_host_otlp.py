@@ -11,7 +11,7 @@ from pathlib import Path
 
 import pytest
 
-from tests.test_host_e2e import ServerProc, _free_port, _http
+from tests.test_host_e2e import _TMP, ServerProc, _free_port, _http
 
 BASE = "http://127.0.0.1:{}"
 
@@ -61,7 +61,7 @@ def otlp_env():
     port = _free_port()
     cfg = f"""
 server:
-  home_dir: "/tmp/hs-e2e-otlp"
+  home_dir: "{_TMP}/hs-e2e-otlp"
 logging:
   default:
     console_level: warn
