@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Isolated kernel microbenchmarks (GPU only) — us/call + achieved GB/s.
 
-Usage: python bench_kernels.py [--which attn|gemm|all] [--iters N]
+Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|all]
+                               [--iters N]
 
 Shapes mirror the flagship bench (Llama-3-8B bf16, bs=256 ctx=512 decode):
 the numbers here are the per-kernel budget lines behind bench.py's step
@@ -124,6 +125,120 @@ def bench_fp8_gemm(iters):
             "us_fp8_mm_only": round(us_fp8_mm, 1)}), flush=True)
 
 
+def _paged_prefill_inputs(seqs, ctx, n, kvh, group, fp8, dev, gen_seed=0):
+    """One step of `seqs` sequences, each `n` rows at positions ctx..ctx+n-1
+    over a randomly paged cache that already holds positions 0..ctx+n-1."""
+    D, BS = 128, 16
+    torch.manual_seed(gen_seed)
+    nblk = (ctx + n + BS - 1) // BS
+    tot = seqs * nblk + 3
+    kc = torch.randn(tot, kvh, BS, D, device=dev)
+    vc = torch.randn(tot, kvh, BS, D, device=dev) * 0.5
+    dt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+    kc, vc = kc.to(dt), vc.to(dt)
+    q = (torch.randn(seqs * n, kvh * group, D, device=dev) * 0.5).bfloat16()
+    bt = torch.randperm(seqs * nblk, device=dev, dtype=torch.int32) \
+        .view(seqs, nblk).contiguous()
+    seq_start = torch.arange(seqs + 1, dtype=torch.int32, device=dev) * n
+    ctx_start = torch.full((seqs,), ctx, dtype=torch.int32, device=dev)
+    pos = torch.arange(ctx, ctx + n, dtype=torch.int32, device=dev)
+    ctx_lens = (pos + 1).repeat(seqs).contiguous()
+    row_seq = torch.arange(seqs, dtype=torch.int32, device=dev) \
+        .repeat_interleave(n).contiguous()
+    return dict(q=q, kc=kc, vc=vc, bt=bt, seq_start=seq_start,
+                ctx_start=ctx_start, ctx_lens=ctx_lens, row_seq=row_seq,
+                n=n, scale=D ** -0.5)
+
+
+def bench_prefill_paged(iters):
+    """MFMA flash prefill over the paged cache vs the per-row paged kernel
+    (unchanged code = the baseline it replaces on continuation steps), on
+    identical tensors in one process.  Llama-3-8B heads (H=32, KV=8).
+
+    Per shape: both kernels warmed, then REPS windows of each, alternating
+    (new, per-row, new, ...) so clock drift and neighbours hit both; the
+    window length adapts to ~WINDOW_S of device time (the per-row kernel
+    spans 4 orders of magnitude over these shapes).  Prints the median and
+    the min..max spread of the windows."""
+    from hyperspot import _C
+    from hyperspot.ops import torch_ref
+    dev = "cuda:0"
+    KVH, GROUP = 8, 4
+    REPS, WINDOW_S = 3, 0.2
+
+    def run_new(t, out):
+        _C.attn_prefill_paged_mfma(out, t["q"], t["kc"], t["vc"], t["bt"],
+                                   t["seq_start"], t["ctx_start"], t["n"],
+                                   t["scale"])
+
+    def run_row(t, out):
+        _C.paged_attn(out, t["q"], t["kc"], t["vc"], t["bt"], t["ctx_lens"],
+                      t["row_seq"], t["scale"], None, 1)
+
+    # one correctness check per cache dtype against the fp32 reference
+    for fp8 in (False, True):
+        t = _paged_prefill_inputs(2, 200, 300, KVH, GROUP, fp8, dev)
+        out = torch.empty_like(t["q"])
+        run_new(t, out)
+        ref = torch_ref.prefill_attn_paged(
+            t["q"].float().cpu(), t["kc"].float().cpu(),
+            t["vc"].float().cpu(), t["bt"].cpu(), t["ctx_lens"].cpu(),
+            t["row_seq"].cpu(), t["scale"])
+        err = (out.float().cpu() - ref).abs().max().item()
+        print(json.dumps({"kernel": "attn_prefill_paged_mfma", "check":
+                          "torch_ref", "kv": "fp8" if fp8 else "bf16",
+                          "max_abs_err": round(err, 5)}), flush=True)
+        assert err < 2.5e-2, err
+
+    def window(fn, k):
+        s = torch.cuda.Event(enable_timing=True)
+        e = torch.cuda.Event(enable_timing=True)
+        s.record()
+        for _ in range(k):
+            fn()
+        e.record()
+        torch.cuda.synchronize()
+        return s.elapsed_time(e) * 1e3 / k  # us/call
+
+    for fp8 in (False, True):
+        for seqs in (1, 8):
+            for ctx in (0, 2048, 8192):
+                for n in (1, 16, 64, 256, 2048):
+                    t = _paged_prefill_inputs(seqs, ctx, n, KVH, GROUP, fp8,
+                                              dev)
+                    o_new = torch.empty_like(t["q"])
+                    o_row = torch.empty_like(t["q"])
+                    fns = {"new": lambda: run_new(t, o_new),
+                           "row": lambda: run_row(t, o_row)}
+                    k = {}
+                    for name, fn in fns.items():
+                        window(fn, 3)                      # warm-up
+                        est = window(fn, 3)
+                        k[name] = int(min(max(WINDOW_S * 1e6 / est, 5),
+                                          max(iters, 5) * 200))
+                    diff = (o_new.float() - o_row.float()).abs().max().item()
+                    us = {"new": [], "row": []}
+                    for _ in range(REPS):
+                        for name, fn in fns.items():
+                            us[name].append(window(fn, k[name]))
+                    med = {a: sorted(v)[len(v) // 2] for a, v in us.items()}
+                    print(json.dumps({
+                        "kernel": "prefill_paged",
+                        "kv": "fp8" if fp8 else "bf16",
+                        "shape": f"seqs{seqs}_ctx{ctx}_n{n}",
+                        "us_mfma": round(med["new"], 1),
+                        "us_per_row": round(med["row"], 1),
+                        "per_row_over_mfma": round(med["row"] / med["new"],
+                                                   2),
+                        "spread_mfma": [round(min(us["new"]), 1),
+                                        round(max(us["new"]), 1)],
+                        "spread_per_row": [round(min(us["row"]), 1),
+                                           round(max(us["row"]), 1)],
+                        "iters": [k["new"], k["row"]],
+                        "max_abs_diff": round(diff, 5)}), flush=True)
+                    del t, o_new, o_row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="attn")
@@ -136,6 +251,8 @@ def main():
         bench_gemm(args.iters)
     if args.which in ("fp8", "all"):
         bench_fp8_gemm(args.iters)
+    if args.which in ("prefill_paged", "all"):
+        bench_prefill_paged(args.iters)
 
 
 if __name__ == "__main__":

@@ -26,6 +26,10 @@ void launch_paged_attn(bf16*, const bf16*, const bf16*, const bf16*,
 void launch_attn_prefill_mfma(bf16*, const bf16*, const bf16*,
                               const bf16*, const int*, int, int, int, int,
                               int, float, long, long, long, hipStream_t);
+void launch_attn_prefill_paged_mfma(bf16*, const bf16*, const bf16*,
+                                    const bf16*, const int*, const int*,
+                                    const int*, int, int, int, int, int, int,
+                                    int, float, long, bool, hipStream_t);
 void launch_silu_mul(bf16*, const bf16*, long, int, hipStream_t);
 void launch_quant_fp8(unsigned char*, float*, const bf16*, long, int, long,
                       hipStream_t);
@@ -169,6 +173,60 @@ void attn_prefill_mfma(torch::Tensor out, torch::Tensor q, torch::Tensor k,
       bf(out), cbf(q), cbf(k), cbf(v), seq_start.data_ptr<int>(),
       (int)seq_start.numel() - 1, (int)max_seqlen, H, KV, D, (float)scale,
       q.stride(0), k.stride(0), v.stride(0), stream());
+}
+
+// Flash prefill over the paged cache: sequence z owns q rows
+// seq_start[z]..seq_start[z+1]-1 at positions ctx_start[z]+i.  Nothing here
+// reads device data: the caller vouches that block_tables covers
+// ceil((ctx_start[z] + n_z) / 16) pages per sequence.
+void attn_prefill_paged_mfma(torch::Tensor out, torch::Tensor q,
+                             torch::Tensor k_cache, torch::Tensor v_cache,
+                             torch::Tensor block_tables,
+                             torch::Tensor seq_start,
+                             torch::Tensor ctx_start, long max_seqlen,
+                             double scale) {
+  check(out, torch::kBFloat16, "out");
+  check_qkv_view(q, "q");
+  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(),
+              "out must be [T, H, D] like q");
+  TORCH_CHECK(q.size(2) == 128,
+              "attn_prefill_paged_mfma: head_dim must be 128, got ",
+              q.size(2));
+  TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() &&
+                  k_cache.is_contiguous() && v_cache.is_contiguous(),
+              "k_cache/v_cache must be contiguous GPU tensors");
+  TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(),
+              "k_cache/v_cache must be [NB, KV, 16, 128] and equal-shaped");
+  TORCH_CHECK(k_cache.size(2) == 16,
+              "attn_prefill_paged_mfma: page size must be 16, got ",
+              k_cache.size(2));
+  TORCH_CHECK(k_cache.size(3) == 128, "cache head_dim must be 128, got ",
+              k_cache.size(3));
+  TORCH_CHECK(v_cache.scalar_type() == k_cache.scalar_type(),
+              "k/v cache dtype mismatch");
+  const bool kv_fp8 = k_cache.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(kv_fp8 || k_cache.scalar_type() == torch::kBFloat16,
+              "cache dtype must be bfloat16 or float8_e4m3fn");
+  const int H = (int)q.size(1), KV = (int)k_cache.size(1);
+  TORCH_CHECK(KV > 0 && H % KV == 0, "GQA group: H=", H,
+              " is no multiple of KV=", KV);
+  check(block_tables, torch::kInt32, "block_tables");
+  check(seq_start, torch::kInt32, "seq_start");
+  check(ctx_start, torch::kInt32, "ctx_start");
+  TORCH_CHECK(seq_start.dim() == 1 && seq_start.numel() >= 1,
+              "seq_start must be [S+1]");
+  const int S = (int)seq_start.numel() - 1;
+  TORCH_CHECK(ctx_start.dim() == 1 && ctx_start.numel() == S,
+              "ctx_start must be [S] with S = seq_start.numel() - 1");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == S,
+              "block_tables must be [S, max_blocks]");
+  TORCH_CHECK(max_seqlen >= 0, "max_seqlen must be >= 0");
+  launch_attn_prefill_paged_mfma(
+      bf(out), cbf(q), cbf(k_cache), cbf(v_cache),
+      block_tables.data_ptr<int>(), seq_start.data_ptr<int>(),
+      ctx_start.data_ptr<int>(), S, (int)max_seqlen, H, KV,
+      (int)q.size(2), (int)block_tables.size(1), (int)k_cache.size(2),
+      (float)scale, q.stride(0), kv_fp8, stream());
 }
 
 void silu_mul(torch::Tensor out, torch::Tensor x) {
@@ -334,6 +392,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_kv_append", &rope_kv_append);
   m.def("paged_attn", &paged_attn);
   m.def("attn_prefill_mfma", &attn_prefill_mfma);
+  m.def("attn_prefill_paged_mfma", &attn_prefill_paged_mfma);
   m.def("silu_mul", &silu_mul);
   m.def("greedy_sample", &greedy_sample);
   m.def("inv_cdf_sample", &inv_cdf_sample);

@@ -75,6 +75,13 @@ _PRESETS = {
         num_kv_heads=2, head_dim=64, intermediate_size=512, vocab_size=512,
         rope_theta=10000.0, max_position=1024,
     ),
+    # tiny-llama at head_dim 128: engine tests reach the 128-dim attention
+    # kernels (MFMA prefill, v3 decode, fp8 KV) without an 8B-shaped model
+    "tiny-llama-d128": ModelSpec(
+        name="tiny-llama-d128", hidden_size=256, num_layers=2, num_heads=4,
+        num_kv_heads=2, head_dim=128, intermediate_size=512, vocab_size=512,
+        rope_theta=10000.0, max_position=1024,
+    ),
     "tiny-moe": ModelSpec(
         name="tiny-moe", hidden_size=256, num_layers=2, num_heads=4,
         num_kv_heads=2, head_dim=64, intermediate_size=256, vocab_size=512,
@@ -113,6 +120,12 @@ class EngineConfig:
     quant: Optional[str] = None          # None (bf16) | "fp8" (e4m3fn weights)
     kv_dtype: str = "bfloat16"           # "bfloat16" | "fp8" (e4m3fn cache)
     enable_prefix_caching: bool = False  # shared-prompt KV block reuse
+    # prefill steps that do not start at position 0 (chunked-prefill
+    # continuations, prefix-cache hits) on the MFMA flash kernel over the
+    # paged cache instead of the per-row kernel.  Off by default: the two
+    # kernels round differently (bf16 vs fp32 P), so turning it on changes
+    # greedy outputs of such steps by bf16-ulp effects
+    prefill_paged_mfma: bool = False
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,

@@ -129,9 +129,11 @@ class ModelRunner:
         bm = self.block_manager
         bs = bm.block_size
         fresh = True
+        ctx_start: List[int] = []
         for si, req in enumerate(batch.requests):
             cs = req.chunk_start
             n = req.chunk_len or req.num_prompt_tokens
+            ctx_start.append(cs)
             if cs > 0:
                 fresh = False      # continuation chunk attends over cache
             ids.extend(req.prompt_token_ids[cs:cs + n])
@@ -158,6 +160,8 @@ class ModelRunner:
             max_seqlen=max((r.chunk_len or r.num_prompt_tokens)
                            for r in batch.requests),
             fresh_prefill=fresh,
+            ctx_start=torch.tensor(ctx_start, dtype=torch.int32, device=d),
+            paged_mfma=self.config.prefill_paged_mfma,
             row_seq=torch.tensor(row_seq, dtype=torch.int32, device=d),
             ctx_lens=(positions + 1).to(torch.int32),
             block_tables=bt.to(d),

@@ -49,9 +49,16 @@ class ForwardMeta:
     return_hidden: bool = False
     # prefill: True when every row starts at position 0 (chunk == whole
     # prompt) -> the self-contained MFMA flash kernel applies; False for
-    # chunked-prefill continuation batches, which must attend over the
-    # paged cache (per-row ctx_lens)
+    # chunked-prefill continuation / prefix-hit batches, which must attend
+    # over the paged cache (MFMA flash kernel over the cache, or per-row
+    # ctx_lens)
     fresh_prefill: bool = True
+    # prefill: [num_seqs] int32, position of each sequence's first row in
+    # this step (its chunk_start; 0 for a fresh request)
+    ctx_start: Optional[torch.Tensor] = None
+    # prefill, not fresh: run the MFMA flash kernel over the paged cache
+    # (EngineConfig.prefill_paged_mfma) instead of the per-row kernel
+    paged_mfma: bool = False
 
 
 class Attention(nn.Module):

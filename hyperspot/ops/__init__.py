@@ -115,15 +115,51 @@ def paged_attn_decode(q: torch.Tensor, k_cache: torch.Tensor,
                                        seq_lens, scale)
 
 
+# Short-chunk rule for prefill over the paged cache.  A step whose longest
+# chunk is a handful of rows over a long context is decode-shaped: the MFMA
+# kernel runs one workgroup per (sequence, head) serially over the context,
+# the per-row kernel one per (row, kv head).  Measured on MI355X, H=32 KV=8,
+# us/layer (profiles/r03_prefill_paged.md, bf16; fp8 within 10%):
+#   chunk rows   1 seq, ctx 8192      8 seqs, ctx 8192
+#                mfma   per-row       mfma   per-row
+#        1        591     212          597     232
+#       16        593     227          600     508
+#       64        597     271          617    1657
+#      256        612     862          691    6516
+# At <= 16 rows the per-row kernel wins every measured shape; at 64 it
+# depends on the sequence count (loses 2.7x at 8 sequences, wins 2.2x at
+# one); from 256 on the MFMA kernel wins everywhere.  The gate reads the
+# host integer meta.max_seqlen only: shapes-only, capture-safe.
+_PAGED_MFMA_MAX_PER_ROW = 16
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
               k_cache: torch.Tensor, v_cache: torch.Tensor, meta,
               scale: float) -> torch.Tensor:
-    """Attention for one layer, prefill or decode, reading the paged cache.
+    """Attention for one layer, prefill or decode.
 
-    The ONE gfx950 kernel serves both modes: decode rows attend over
-    ctx=seq_len cache slots; prefill rows attend over slots 0..pos (their
-    own k/v were appended by the fused RoPE kernel just before), which
-    realises causal varlen attention without a separate kernel.
+    Three gfx950 kernels, picked from shapes and step metadata only (no
+    device read, so every choice is hipGraph-capture-safe):
+
+    - decode: ``paged_attn``, one workgroup per (row, kv head) streaming
+      the sequence's pages; rows attend over ctx=seq_len cache slots.
+    - fresh prefill (every row of the step starts at position 0), head
+      dim 128: ``attn_prefill_mfma``, MFMA flash attention reading K/V
+      straight from the qkv projection.
+    - any other head-dim-128 prefill step (a chunked-prefill continuation,
+      the remainder after a prefix-cache hit, and whatever fresh requests
+      are packed beside them), when ``meta.paged_mfma`` is set
+      (``EngineConfig.prefill_paged_mfma``): ``attn_prefill_paged_mfma``,
+      the same flash structure reading K/V from the paged cache, bf16 or
+      fp8.  The fused RoPE kernel has appended the step's own k/v just
+      before, so rows attend over slots 0..pos.  Steps whose longest chunk
+      is at most ``_PAGED_MFMA_MAX_PER_ROW`` rows are decode-shaped and
+      stay on ``paged_attn`` (measurement beside the constant).
+
+    Without ``meta.paged_mfma`` (the default: the two kernels round
+    differently, and a serving default must not change what a deployment
+    computes) and for other head dims, such steps run ``paged_attn`` with
+    per-row ctx_lens.
     """
     if meta.mode == "decode":
         return paged_attn_decode(q, k_cache, v_cache, meta.block_tables,
@@ -134,9 +170,19 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
             # MFMA flash prefill (K/V straight from the qkv projection)
             _native().attn_prefill_mfma(out, q, k, v, meta.seq_start,
                                         meta.max_seqlen, scale)
+        elif q.shape[-1] == 128 and getattr(meta, "paged_mfma", False) \
+                and meta.max_seqlen > _PAGED_MFMA_MAX_PER_ROW:
+            # MFMA flash prefill over the (freshly appended) paged cache
+            if meta.ctx_start is None:
+                raise RuntimeError(
+                    "prefill over the paged cache needs meta.ctx_start")
+            _native().attn_prefill_paged_mfma(
+                out, q, k_cache, v_cache, meta.block_tables, meta.seq_start,
+                meta.ctx_start, meta.max_seqlen, scale)
         else:
-            # per-row attention over the (freshly appended) paged cache:
-            # chunked-prefill continuation rows or odd head dims
+            # per-row attention over the paged cache: the default for
+            # continuation steps, odd head dims, and decode-shaped steps
+            # (short-chunk rule above)
             _native().paged_attn(out, q, k_cache, v_cache,
                                  meta.block_tables, meta.ctx_lens,
                                  meta.row_seq, scale, None, 1)

@@ -825,6 +825,10 @@ def main():
     ap.add_argument("--quant", default=None, choices=["fp8"])
     ap.add_argument("--kv-dtype", default="bfloat16",
                     choices=["bfloat16", "fp8"])
+    ap.add_argument("--prefill-paged-mfma", action="store_true",
+                    help="run chunked-prefill continuation / prefix-hit "
+                         "steps on the MFMA flash kernel over the paged "
+                         "cache (EngineConfig.prefill_paged_mfma)")
     args = ap.parse_args()
 
     logging.basicConfig(level=logging.INFO,
@@ -843,7 +847,8 @@ def main():
         max_model_len=args.max_model_len,
         num_gpu_blocks=args.num_gpu_blocks or None,
         enforce_eager=args.eager or not on_gpu, tp_size=args.tp,
-        quant=args.quant, kv_dtype=args.kv_dtype)
+        quant=args.quant, kv_dtype=args.kv_dtype,
+        prefill_paged_mfma=args.prefill_paged_mfma)
     rank = 0
     # MoE models shard experts over the same ranks as TP attention
     # (config 4: Mixtral EP over RCCL all-to-all).  Decode graphs stay ON
