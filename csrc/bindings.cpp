@@ -50,6 +50,8 @@ void launch_moe_gemm_fp8(bf16*, float*, const unsigned char*, const float*,
 void launch_greedy_sample(long*, const bf16*, long, int, hipStream_t);
 void launch_inv_cdf_sample(long*, const float*, const float*, long, int,
                            hipStream_t);
+void launch_decode_advance(long*, long*, int*, long*, int*, const long*,
+                           const int*, int, int, int, hipStream_t);
 
 namespace {
 
@@ -254,6 +256,35 @@ void inv_cdf_sample(torch::Tensor out, torch::Tensor logits,
                         (int)logits.size(1), stream());
 }
 
+void decode_advance(torch::Tensor input_ids, torch::Tensor positions,
+                    torch::Tensor seq_lens, torch::Tensor slot_mapping,
+                    torch::Tensor block_tables, torch::Tensor sampled_prev,
+                    torch::Tensor ctl, int64_t page) {
+  check(input_ids, torch::kInt64, "input_ids");
+  check(positions, torch::kInt64, "positions");
+  check(seq_lens, torch::kInt32, "seq_lens");
+  check(slot_mapping, torch::kInt64, "slot_mapping");
+  check(block_tables, torch::kInt32, "block_tables");
+  check(sampled_prev, torch::kInt64, "sampled_prev");
+  check(ctl, torch::kInt32, "ctl");
+  const int64_t rows = input_ids.numel();
+  TORCH_CHECK(rows > 0 && page > 0, "empty decode_advance");
+  TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == rows,
+              "block_tables must be [rows, max_blocks]");
+  TORCH_CHECK(positions.numel() == rows && seq_lens.numel() == rows &&
+                  slot_mapping.numel() == rows &&
+                  sampled_prev.numel() == rows,
+              "per-row tensors must have `rows` elements");
+  TORCH_CHECK(ctl.numel() >= 4 * rows + 1, "ctl must hold 4*rows+1 ints");
+  launch_decode_advance(input_ids.data_ptr<long>(), positions.data_ptr<long>(),
+                        seq_lens.data_ptr<int>(),
+                        slot_mapping.data_ptr<long>(),
+                        block_tables.data_ptr<int>(),
+                        sampled_prev.data_ptr<long>(), ctl.data_ptr<int>(),
+                        (int)rows, (int)block_tables.size(1), (int)page,
+                        stream());
+}
+
 }  // namespace
 
 
@@ -396,4 +427,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &silu_mul);
   m.def("greedy_sample", &greedy_sample);
   m.def("inv_cdf_sample", &inv_cdf_sample);
+  m.def("decode_advance", &decode_advance);
 }

@@ -126,6 +126,9 @@ class EngineConfig:
     # kernels round differently (bf16 vs fp32 P), so turning it on changes
     # greedy outputs of such steps by bf16-ulp effects
     prefill_paged_mfma: bool = False
+    # enqueue decode step n+1 before step n's tokens reach the host
+    # (LLMEngine.step_pipelined); same tokens and finish reasons either way
+    pipeline_decode: bool = True
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,

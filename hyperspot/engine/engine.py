@@ -30,6 +30,7 @@ class LLMEngine:
         self.scheduler = Scheduler(config, self.runner.block_manager)
         self.eos_token_id = eos_token_id
         self._id_counter = itertools.count()
+        self._inflight = None           # enqueued, uncollected PipeStep
         log.info("engine up: model=%s blocks=%d device=%s (%.1fs)",
                  config.model, self.runner.num_blocks, self.runner.device,
                  time.monotonic() - t0)
@@ -47,10 +48,18 @@ class LLMEngine:
         return rid
 
     def abort_request(self, request_id: str) -> None:
-        self.scheduler.abort(request_id)
+        h = self._inflight
+        if h is not None and h.runs(request_id):
+            # the enqueued step may still write this row's pages: they go
+            # back to the pool when that step has been collected
+            self.scheduler.abort(request_id, free=False)
+            h.deferred_free.append(request_id)
+        else:
+            self.scheduler.abort(request_id)
+        self.runner.pipe_drop(request_id)
 
     def has_work(self) -> bool:
-        return self.scheduler.has_work()
+        return self.scheduler.has_work() or self._inflight is not None
 
     @property
     def num_running(self) -> int:
@@ -61,11 +70,16 @@ class LLMEngine:
         return len(self.scheduler.waiting)
 
     def step(self) -> List[StepOutput]:
+        """Run one step synchronously and return its outputs (after those
+        of a pipelined step still in flight, if there is one)."""
+        outputs: List[StepOutput] = self.drain()
         batch = self.scheduler.schedule()
         if batch.empty:
-            return []
+            return outputs
         tokens = self.runner.execute(batch)
-        outputs: List[StepOutput] = []
+        # the synchronous path fills the decode inputs from the host; the
+        # next pipelined step re-seeds the device state
+        self.runner.pipe_invalidate()
         bm = self.runner.block_manager
         for req, tok in zip(batch.requests, tokens.tolist()):
             if batch.mode == "prefill" and bm.enable_prefix_caching:
@@ -79,6 +93,81 @@ class LLMEngine:
             outputs.append(StepOutput(req.request_id, int(tok), req.finished,
                                       req.finish_reason))
         self.scheduler.finish_step()
+        return outputs
+
+    # ---- pipelined stepping (depth one) ----
+
+    def _pipe_eligible(self) -> bool:
+        """Every running row greedy and unguided: the next decode step's
+        inputs then depend on the in-flight tokens only through input_ids,
+        which the device already holds."""
+        for r in self.scheduler.running:
+            sp = r.sampling
+            if sp.temperature != 0 or sp.response_schema is not None \
+                    or sp.response_format in ("json", "tool_call"):
+                return False
+        return True
+
+    def step_pipelined(self) -> List[StepOutput]:
+        """Enqueue decode step n+1, then wait for and return the outputs
+        of step n ([] while the pipeline fills).  Whatever the fast path
+        does not cover (a prefill, a stochastic or guided row, preemption,
+        tensor parallelism) first drains, then takes step().  A row that
+        reaches max_tokens in the in-flight step is left out of the next
+        one; EOS / stop tokens are seen one step late, and the token of
+        that extra step is dropped, so streams and finish reasons are
+        those of step()."""
+        cfg = self.config
+        sch = self.scheduler
+        rn = self.runner
+        fast = (cfg.pipeline_decode and cfg.tp_size == 1
+                and not sch.waiting and bool(sch.running))
+        seed = None
+        if fast and (not rn.pipe_valid() or rn.pipe_stale()):
+            if self._inflight is not None:
+                return self.drain()
+            fast = self._pipe_eligible()
+            seed = sch.running
+        if fast:
+            h = rn.pipe_launch(seed)
+            if h is not None:
+                prev, self._inflight = self._inflight, h
+                return self._collect(prev) if prev is not None else []
+        if self._inflight is not None:
+            return self.drain()
+        return self.step()
+
+    def drain(self) -> List[StepOutput]:
+        """Outputs of the step in flight, if any; the pipeline is empty
+        afterwards."""
+        h, self._inflight = self._inflight, None
+        return self._collect(h) if h is not None else []
+
+    def _collect(self, h) -> List[StepOutput]:
+        outputs: List[StepOutput] = []
+        done = []
+        eos = self.eos_token_id
+        for req, tok in self.runner.pipe_collect(h):
+            if req.finished:
+                continue   # stopped one step earlier, or aborted: dropped
+            req.append_output(tok, eos)
+            outputs.append(StepOutput(req.request_id, tok, req.finished,
+                                      req.finish_reason))
+            if req.finished:
+                done.append(req)
+        bm = self.runner.block_manager
+        if done:
+            nxt = self._inflight
+            for r in done:
+                self.runner.pipe_drop(r.request_id)
+                if nxt is not None and nxt.runs(r.request_id):
+                    nxt.deferred_free.append(r.request_id)
+                else:
+                    bm.free(r.request_id)
+            self.scheduler.running = [r for r in self.scheduler.running
+                                      if not r.finished]
+        for rid in h.deferred_free:
+            bm.free(rid)
         return outputs
 
     def capture_graphs(self) -> None:

@@ -59,6 +59,26 @@ def _load_tunableop_results() -> None:
         log.warning("TunableOp load failed: %s", e)
 
 
+class PipeStep:
+    """One enqueued pipelined decode step: the rows it runs (slot order),
+    the staging slot its tokens land in, and the sequences whose pages may
+    only be freed once it has been collected."""
+
+    __slots__ = ("reqs", "slots", "ring", "deferred_free", "_rids")
+
+    def __init__(self, reqs, slots, ring):
+        self.reqs = reqs
+        self.slots = slots
+        self.ring = ring
+        self.deferred_free: List[str] = []
+        self._rids = None
+
+    def runs(self, request_id: str) -> bool:
+        if self._rids is None:
+            self._rids = {r.request_id for r in self.reqs}
+        return request_id in self._rids
+
+
 class ModelRunner:
     def __init__(self, config: EngineConfig, device: Optional[str] = None):
         self.config = config
@@ -114,6 +134,21 @@ class ModelRunner:
         self._pgraphs: Dict[int, torch.cuda.CUDAGraph] = {}
         self._pgraph_io: Dict[int, dict] = {}
         self._graph_pool = None
+        # pipelined decode: device state of the current bucket (None = the
+        # next pipelined step re-seeds it from the host), io tensors of the
+        # eager twin, and a ring of pinned staging slots.  A slot is read
+        # (ctl H2D) and written (token D2H) when the copy EXECUTES; with a
+        # depth-one pipeline at most two steps are uncollected, so four
+        # slots keep the host off anything a queued copy still touches.
+        self._pipe: Optional[dict] = None
+        self._pipe_eager_io: Optional[dict] = None
+        self._pipe_seq = 0
+        self._pipe_ring = [
+            {"ctl": torch.empty(4 * cap + 4, dtype=torch.int32,
+                                pin_memory=pin),
+             "tok": torch.empty(cap, dtype=torch.long, pin_memory=pin),
+             "event": torch.cuda.Event() if pin else None}
+            for _ in range(4)]
 
     # ---------------- input preparation ----------------
 
@@ -299,6 +334,10 @@ class ModelRunner:
         if bucket not in self._graphs:
             self._capture(bucket)
         io = self._graph_io[bucket]
+        if not io["passthrough"]:
+            # the graph's head kernel leaves host-filled inputs alone
+            io["ctl"][4 * bucket:].fill_(-1)
+            io["passthrough"] = True
         io["input_ids"][:B] = input_ids
         io["input_ids"][B:] = 0
         io["positions"][:B] = meta.positions
@@ -328,6 +367,13 @@ class ModelRunner:
             "block_tables": torch.zeros(bucket, self.max_blocks_per_seq,
                                         dtype=torch.int32, device=d),
             "seq_lens": torch.ones(bucket, dtype=torch.int32, device=d),
+            # pipelined stepping: the previous step's argmax and the
+            # per-step control block of decode_advance (n_live < 0 =
+            # pass-through, the synchronous path fills the inputs itself)
+            "sampled": torch.zeros(bucket, dtype=torch.long, device=d),
+            "ctl": torch.full((4 * bucket + 4,), -1, dtype=torch.int32,
+                              device=d),
+            "passthrough": True,
         }
         meta = ForwardMeta(mode="decode", positions=io["positions"],
                            slot_mapping=io["slot_mapping"],
@@ -335,11 +381,18 @@ class ModelRunner:
                            seq_lens=io["seq_lens"])
         # warmup outside capture (allocator, hipBLASLt heuristics, RCCL)
         for _ in range(2):
-            self.model(io["input_ids"], meta, self.kv_caches)
+            self._pipe_head(io)
+            ops.greedy_sample(
+                self.model(io["input_ids"], meta, self.kv_caches),
+                out=io["sampled"])
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self._graph_pool):
+            # head: per-step inputs derived on the device; tail: greedy
+            # argmax into the buffer the next replay's head reads
+            self._pipe_head(io)
             io["logits"] = self.model(io["input_ids"], meta, self.kv_caches)
+            ops.greedy_sample(io["logits"], out=io["sampled"])
         if self._graph_pool is None:
             self._graph_pool = g.pool()
         self._graphs[bucket] = g
@@ -360,6 +413,177 @@ class ModelRunner:
                     and t <= self.config.max_model_len
                     and t not in self._pgraphs):
                 self._capture_prefill(t)
+
+    # ---------------- pipelined decode ----------------
+    #
+    # A decode step whose inputs do not depend on the tokens still in flight
+    # is enqueued from lengths alone: decode_advance (head of the graph)
+    # derives ids / positions / slots / table updates on the device from
+    # the previous step's argmax (tail of the graph).  Rows keep their slot
+    # in the bucket for as long as the device state lives; a row that leaves
+    # becomes a padding row in place, and the state is re-seeded from the
+    # host (every row on the host-id path, rows compacted) after any
+    # synchronous step or when the live rows fit a smaller bucket.
+
+    def _pipe_head(self, io: dict) -> None:
+        ops.decode_advance(io["input_ids"], io["positions"], io["seq_lens"],
+                           io["slot_mapping"], io["block_tables"],
+                           io["sampled"], io["ctl"], self.config.block_size)
+
+    def pipe_invalidate(self) -> None:
+        self._pipe = None
+
+    def pipe_valid(self) -> bool:
+        return self._pipe is not None
+
+    def pipe_drop(self, request_id: str) -> None:
+        """The row takes part in no further pipelined step."""
+        p = self._pipe
+        if p is not None:
+            s = p["slot_of"].get(request_id)
+            if s is not None:
+                p["alive"][s] = False
+
+    def pipe_stale(self) -> bool:
+        """Enough rows left that the rest fit a smaller bucket."""
+        p = self._pipe
+        if p is None:
+            return False
+        n = int(p["alive"].sum())
+        if n == 0:
+            return False
+        if p["graph"]:
+            return self._bucket_for(n) != p["bucket"]
+        return n * 2 <= len(p["reqs"])
+
+    def _pipe_seed(self, reqs: List[Request]) -> None:
+        import numpy as np
+        bm = self.block_manager
+        B = len(reqs)
+        bucket = self._bucket_for(B)
+        graph = (bucket is not None and self.device.type == "cuda"
+                 and not self.config.enforce_eager)
+        if graph:
+            if bucket not in self._graphs:
+                self._capture(bucket)
+            io = self._graph_io[bucket]
+            nrows = bucket
+        else:
+            full = self._pipe_eager_io
+            if full is None:
+                cap, d = bm.capacity, self.device
+                full = self._pipe_eager_io = {
+                    "input_ids": torch.zeros(cap, dtype=torch.long, device=d),
+                    "positions": torch.zeros(cap, dtype=torch.long, device=d),
+                    "slot_mapping": torch.full((cap,), -1, dtype=torch.long,
+                                               device=d),
+                    "block_tables": torch.zeros(cap, self.max_blocks_per_seq,
+                                                dtype=torch.int32, device=d),
+                    "seq_lens": torch.ones(cap, dtype=torch.int32, device=d),
+                    "sampled": torch.zeros(cap, dtype=torch.long, device=d),
+                    "ctl": torch.full((4 * cap + 4,), -1, dtype=torch.int32,
+                                      device=d),
+                }
+            nrows = B
+            io = {k: v[:nrows] for k, v in full.items() if k != "ctl"}
+            io["ctl"] = full["ctl"][:4 * nrows + 4]
+        self._pipe = {
+            "graph": graph, "bucket": bucket, "io": io, "nrows": nrows,
+            "reqs": list(reqs), "fresh": True,
+            "slot_of": {r.request_id: i for i, r in enumerate(reqs)},
+            "rows": np.fromiter((bm.row_of[r.request_id] for r in reqs),
+                                dtype=np.int64, count=B),
+            "alive": np.ones(B, dtype=bool),
+            # steps the row may still be launched for
+            "remaining": np.fromiter(
+                (r.sampling.max_tokens - r.num_generated for r in reqs),
+                dtype=np.int64, count=B),
+        }
+
+    @torch.inference_mode()
+    def pipe_launch(self, seed_reqs: Optional[List[Request]] = None):
+        """Enqueue one decode step without waiting for the previous one.
+
+        seed_reqs: re-seed the device state from these requests first (only
+        with nothing in flight).  Returns a handle for pipe_collect, or None
+        when no step was enqueued: no row has a token left to produce, or
+        the pool cannot give every page-starting row its page (the caller
+        falls back to the synchronous step, which may preempt)."""
+        import numpy as np
+        bm = self.block_manager
+        bs = bm.block_size
+        if seed_reqs is not None:
+            self._pipe_seed(seed_reqs)
+        p = self._pipe
+        idx = np.nonzero(p["alive"] & (p["remaining"] > 0))[0]
+        if idx.size == 0:
+            return None
+        rows = p["rows"][idx]
+        n = bm.tokens_np[rows].copy()            # this step's positions
+        boundary = n % bs == 0
+        if int(boundary.sum()) > bm.num_free:
+            if p["fresh"]:
+                self._pipe = None
+            return None
+        bm.append_slots_batch(rows)
+        R = p["nrows"]
+        io = p["io"]
+        ring = self._pipe_ring[self._pipe_seq % len(self._pipe_ring)]
+        self._pipe_seq += 1
+        ctl = ring["ctl"].numpy()[:4 * R + 4]
+        c = ctl[:4 * R].reshape(4, R)
+        c[0].fill(-2)
+        c[1].fill(-1)
+        d = self.device
+        nb = d.type == "cuda"
+        if p["fresh"]:
+            reqs = p["reqs"]
+            c[0][idx] = -1
+            c[2][idx] = np.fromiter((reqs[i].last_token_id for i in idx),
+                                    dtype=np.int64, count=idx.size)
+            c[3][idx] = n
+            max_nt = int(bm.ntables_np[rows].max())
+            bt_stage = self._st_bt_flat[:idx.size * max_nt].view(
+                idx.size, max_nt)
+            bt_stage.numpy()[:] = bm.tables_np[
+                rows[:, None], np.arange(max_nt)[None, :]]
+            # a fresh state holds every row, in order: idx == arange(B)
+            io["block_tables"][:idx.size, :max_nt] = \
+                bt_stage.to(d, non_blocking=nb)
+            p["fresh"] = False
+        else:
+            c[0][idx] = idx
+            c[1][idx[boundary]] = bm.tables_np[rows[boundary],
+                                               n[boundary] // bs]
+        ctl[4 * R] = int(idx[-1]) + 1
+        io["ctl"].copy_(ring["ctl"][:4 * R + 4], non_blocking=nb)
+        if p["graph"]:
+            io["passthrough"] = False
+            self._graphs[p["bucket"]].replay()
+        else:
+            self._pipe_head(io)
+            meta = ForwardMeta(mode="decode", positions=io["positions"],
+                               slot_mapping=io["slot_mapping"],
+                               block_tables=io["block_tables"],
+                               seq_lens=io["seq_lens"])
+            ops.greedy_sample(
+                self.model(io["input_ids"], meta, self.kv_caches),
+                out=io["sampled"])
+        # token D2H behind the step on the same stream, outside the graph
+        ring["tok"][:R].copy_(io["sampled"], non_blocking=nb)
+        if nb:
+            ring["event"].record()
+        p["remaining"][idx] -= 1
+        return PipeStep([p["reqs"][i] for i in idx], idx, ring)
+
+    def pipe_collect(self, step: "PipeStep"):
+        """Wait for the step's tokens (its own event, never a device-wide
+        sync); returns [(request, token_id)] in slot order."""
+        ev = step.ring["event"]
+        if ev is not None:
+            ev.synchronize()
+        toks = step.ring["tok"].numpy()[step.slots].tolist()
+        return zip(step.reqs, toks)
 
     # ---------------- embeddings ----------------
 

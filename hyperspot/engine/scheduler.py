@@ -45,14 +45,16 @@ class Scheduler:
     def add(self, req: Request) -> None:
         self.waiting.append(req)
 
-    def abort(self, request_id: str) -> None:
+    def abort(self, request_id: str, free: bool = True) -> None:
+        """free=False leaves the pages to the caller (an enqueued step may
+        still write them)."""
         for q in (self.waiting, self.running):
             for r in list(q):
                 if r.request_id == request_id:
                     q.remove(r)
                     # a mid-prefill (chunked) request holds pages while
                     # still in `waiting` — free by ownership, not state
-                    if r.request_id in self.bm.row_of:
+                    if free and r.request_id in self.bm.row_of:
                         self.bm.free(r.request_id)
                     r.state = RequestState.FINISHED
 
@@ -127,12 +129,17 @@ class Scheduler:
         batch = ScheduledBatch(mode="decode")
         # Ensure every running sequence can take one more token; preempt
         # (recompute) the youngest sequences if the pool is out of pages.
-        while self.running:
+        import numpy as np
+        bm = self.bm
+        # a step needs at most one fresh block per sequence: with that many
+        # free the per-row count is not needed at all
+        while self.running and len(self.running) > bm.num_free:
             # total fresh-block demand of this decode step vs the free list
-            need = sum(1 for req in self.running
-                       if self.bm.tokens_of(req.request_id)
-                       % self.bm.block_size == 0)
-            if need <= self.bm.num_free:
+            rows = np.fromiter((bm.row_of[r.request_id]
+                                for r in self.running), dtype=np.int64,
+                               count=len(self.running))
+            need = int((bm.tokens_np[rows] % bm.block_size == 0).sum())
+            if need <= bm.num_free:
                 break
             victim = self.running.pop()          # youngest (appended last)
             self.bm.free(victim.request_id)
@@ -150,6 +157,8 @@ class Scheduler:
     def finish_step(self) -> List[Request]:
         """Remove finished requests from running, free their pages."""
         done = [r for r in self.running if r.finished]
+        if not done:                 # the usual step: one pass, no rebuild
+            return done
         for r in done:
             self.bm.free(r.request_id)
         self.running = [r for r in self.running if not r.finished]

@@ -349,13 +349,39 @@ def moe_ffn_fp8(xq: "QTensor", w13q: torch.Tensor, w13s: torch.Tensor,
     return out
 
 
-def greedy_sample(logits: torch.Tensor) -> torch.Tensor:
+def greedy_sample(logits: torch.Tensor,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Row-wise argmax; `out` (int64 [rows]) is written in place when given
+    (the captured decode graph samples into its persistent buffer)."""
     if logits.is_cuda:
-        out = torch.empty(logits.shape[0], dtype=torch.long,
-                          device=logits.device)
+        if out is None:
+            out = torch.empty(logits.shape[0], dtype=torch.long,
+                              device=logits.device)
         _native().greedy_sample(out, logits)
         return out
-    return logits.float().argmax(-1)
+    res = logits.float().argmax(-1)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res
+
+
+def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
+                   seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
+                   block_tables: torch.Tensor, sampled_prev: torch.Tensor,
+                   ctl: torch.Tensor, page: int) -> None:
+    """Derive one decode step's inputs on the device (csrc/decode_state.hip).
+
+    In place on the per-row state (positions i64, seq_lens i32, block_tables
+    i32 [rows, max_blocks]) and the forward's inputs (input_ids, slot_mapping
+    i64).  ctl is int32 [4*rows + 4]: src_idx | new_blk | host_ids | host_pos
+    | n_live — see the kernel's header for the row semantics."""
+    if input_ids.is_cuda:
+        _native().decode_advance(input_ids, positions, seq_lens, slot_mapping,
+                                 block_tables, sampled_prev, ctl, page)
+        return
+    torch_ref.decode_advance(input_ids, positions, seq_lens, slot_mapping,
+                             block_tables, sampled_prev, ctl, page)
 
 
 def sample(logits: torch.Tensor, temperature: torch.Tensor,

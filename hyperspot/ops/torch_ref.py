@@ -156,6 +156,36 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
     return (torch.nn.functional.silu(g) * u).to(gate_up.dtype)
 
 
+def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
+                   seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
+                   block_tables: torch.Tensor, sampled_prev: torch.Tensor,
+                   ctl: torch.Tensor, page: int) -> None:
+    """Twin of csrc/decode_state.hip (in place, same row semantics)."""
+    rows = input_ids.numel()
+    max_blocks = block_tables.shape[1]
+    n_live = int(ctl[4 * rows])
+    if n_live < 0:
+        return
+    c = ctl[:4 * rows].view(4, rows).long()
+    src, new_blk, host_ids, host_pos = c[0], c[1], c[2], c[3]
+    r = torch.arange(rows, device=input_ids.device)
+    live = (r < n_live) & (src >= -1) & (src < rows)
+    dev = live & (src >= 0)
+    ids = torch.where(dev, sampled_prev[src.clamp(0, rows - 1)], host_ids)
+    pos = torch.where(dev, positions + 1, host_pos)
+    input_ids.copy_(torch.where(live, ids, torch.zeros_like(ids)))
+    positions.copy_(torch.where(live, pos, torch.zeros_like(pos)))
+    seq_lens.copy_(torch.where(live, pos + 1,
+                               torch.ones_like(pos)).to(seq_lens.dtype))
+    bi = torch.div(pos, page, rounding_mode="floor")
+    ok = live & (pos >= 0) & (bi < max_blocks)
+    inst = ok & (new_blk >= 0)
+    block_tables[r[inst], bi[inst]] = new_blk[inst].to(block_tables.dtype)
+    blk = block_tables[r, bi.clamp(0, max_blocks - 1)].long()
+    slot_mapping.copy_(torch.where(ok, blk * page + pos % page,
+                                   torch.full_like(pos, -1)))
+
+
 def sample(logits: torch.Tensor, temperature: torch.Tensor,
            top_p: torch.Tensor, top_k: torch.Tensor,
            uniform: torch.Tensor) -> torch.Tensor:

@@ -124,7 +124,11 @@ class WorkerState:
         executed from a connection thread."""
         if self.tp == 1:
             with self.lock:
-                return self._exec(kind, arg)
+                drained = self.engine.drain()    # never mid-step
+                try:
+                    return self._exec(kind, arg)
+                finally:
+                    self._fanout(drained)
         q = queue.Queue()
         with self.new_work:
             self.pending_exec.append((kind, arg, q))
@@ -274,9 +278,14 @@ class WorkerState:
                 if self.stop:
                     if self.tp > 1:
                         dist.broadcast_object_list([("stop",)], src=0)
+                    self._fanout(self.engine.drain())
                     return
                 if self.bench_req is not None:
                     continue
+                if self.pending_exec:
+                    # model-wide ops run at a step boundary: nothing may
+                    # be in flight
+                    self._fanout(self.engine.drain())
                 while self.pending_exec:
                     kind, arg, q = self.pending_exec.pop(0)
                     dist.broadcast_object_list([("exec", kind, arg)],
@@ -294,14 +303,21 @@ class WorkerState:
                     # token budget queued (same prefill batches on
                     # every run), and decoding resumes with the bench
                     # op (same sequence lengths at the timed window)
+                    self._fanout(self.engine.drain())    # parked = empty
                     self.new_work.wait(timeout=0.02)
                     continue
                 if self.tp > 1:
                     ops = self.pending_ops
                     self.pending_ops = []
                     dist.broadcast_object_list([("step", ops)], src=0)
-                outputs = self.engine.step()
+                # enqueues the next decode step before delivering this
+                # one's tokens; an idle engine drains by itself (has_work
+                # stays true while a step is in flight)
+                outputs = self.engine.step_pipelined()
             self._fanout(outputs)
+        with self.new_work:
+            outputs = self.engine.drain()
+        self._fanout(outputs)
 
     def _fanout(self, outputs):
         # mux path: hand the RAW outputs to the channel's writer thread;
@@ -330,25 +346,32 @@ class WorkerState:
             for mux, raw in per_mux.items():
                 mux.send_outputs(raw)
 
-    def _one_step(self):
+    def _one_step(self, drain=False):
+        """One pipelined engine step (enqueue the next, deliver the one in
+        flight) or, with drain=True, only the delivery of what is in
+        flight.  Returns the number of outputs handed to the streams."""
         import torch.distributed as dist
         self.drain_mux_inputs()
         t0 = time.perf_counter()
         with self.new_work:
             t1 = time.perf_counter()
             self._drain_submits_locked()
-            if self.tp > 1:
-                ops = self.pending_ops
-                self.pending_ops = []
-                dist.broadcast_object_list([("step", ops)], src=0)
-            outputs = self.engine.step()
+            if drain:
+                outputs = self.engine.drain()
+            else:
+                if self.tp > 1:
+                    ops = self.pending_ops
+                    self.pending_ops = []
+                    dist.broadcast_object_list([("step", ops)], src=0)
+                outputs = self.engine.step_pipelined()
         t2 = time.perf_counter()
         self._fanout(outputs)
         t3 = time.perf_counter()
         self._bt_lock += t1 - t0
         self._bt_step += t2 - t1
         self._bt_fanout += t3 - t2
-        self._last_outputs = outputs
+        if outputs or not drain:     # an empty drain delivered no step
+            self._last_outputs = outputs
         return len(outputs)
 
     def _sync(self):
@@ -379,11 +402,15 @@ class WorkerState:
             for _ in range(warmup):
                 self._one_step()
             self._sync()
+            # the pipeline enters the window empty and leaves it empty:
+            # exactly K steps are enqueued, run and delivered in [t0, t1]
+            self._one_step(drain=True)
             self._bt_lock = self._bt_step = self._bt_fanout = 0.0
             t0 = time.time()
             produced = 0
             for _ in range(steps):
                 produced += self._one_step()
+            produced += self._one_step(drain=True)
             self._sync()
             t1 = time.time()
             extra = {}
