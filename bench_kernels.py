@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Isolated kernel microbenchmarks (GPU only) — us/call + achieved GB/s.
 
-Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|all]
+Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|sample|all]
                                [--iters N]
 
 Shapes mirror the flagship bench (Llama-3-8B bf16, bs=256 ctx=512 decode):
@@ -239,6 +239,54 @@ def bench_prefill_paged(iters):
                     del t, o_new, o_row
 
 
+def bench_sample(iters):
+    """Sampling at the decode graph's tail: sample_fused (one kernel on the
+    bf16 logits) against today's ops.sample (fp32 copy, topk, sort, cumsum,
+    argsort, inv_cdf kernel, with its host syncs) and the greedy argmax.
+    GB/s counts one read of the bf16 logits, whatever the op really moves."""
+    import hyperspot.ops as ops
+    dev = "cuda:0"
+    vocab = 128256
+    for rows in (2048, 64):
+        g = torch.Generator().manual_seed(rows)
+        logits = torch.empty(rows, vocab, dtype=torch.bfloat16, device=dev)
+        for r0 in range(0, rows, 256):          # bounded host memory
+            n = min(256, rows - r0)
+            logits[r0:r0 + n] = (torch.randn(n, vocab, generator=g) * 3).to(
+                torch.bfloat16).to(dev)
+        u = torch.rand(rows, generator=g).to(dev)
+        out = torch.empty(rows, dtype=torch.long, device=dev)
+        nbytes = rows * vocab * 2
+
+        def params(t, k, p):
+            return (torch.full((rows,), t, dtype=torch.float32, device=dev),
+                    torch.full((rows,), p, dtype=torch.float32, device=dev),
+                    torch.full((rows,), k, dtype=torch.int32, device=dev))
+
+        cases = [("greedy_sample", None),
+                 ("sample_fused", (0.0, 0, 1.0)),
+                 ("sample_fused", (0.8, 0, 1.0)),
+                 ("sample_fused", (0.8, 40, 0.95)),
+                 ("ops.sample", (0.8, 0, 1.0)),
+                 ("ops.sample", (0.8, 40, 0.95))]
+        for name, tkp in cases:
+            if tkp is None:
+                fn = lambda: ops.greedy_sample(logits, out=out)
+            else:
+                t, p, k = params(*tkp)
+                if name == "sample_fused":
+                    fn = lambda: ops.sample_fused(logits, t, p, k, u, out=out)
+                else:
+                    fn = lambda: ops.sample(logits, t, p, k, u)
+            n_it = iters if name != "ops.sample" else max(iters // 10, 5)
+            us = timed(fn, n_it, warmup=5)
+            print(json.dumps({
+                "kernel": name, "shape": f"{rows}x{vocab}",
+                "t_k_p": tkp, "us": round(us, 1),
+                "GBps_logits": round(nbytes / us / 1e3, 0)}), flush=True)
+        del logits
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="attn")
@@ -253,6 +301,8 @@ def main():
         bench_fp8_gemm(args.iters)
     if args.which in ("prefill_paged", "all"):
         bench_prefill_paged(args.iters)
+    if args.which in ("sample", "all"):
+        bench_sample(args.iters)
 
 
 if __name__ == "__main__":

@@ -50,6 +50,8 @@ void launch_moe_gemm_fp8(bf16*, float*, const unsigned char*, const float*,
 void launch_greedy_sample(long*, const bf16*, long, int, hipStream_t);
 void launch_inv_cdf_sample(long*, const float*, const float*, long, int,
                            hipStream_t);
+void launch_sample_fused(long*, const bf16*, const float*, const float*,
+                         const int*, const float*, long, int, hipStream_t);
 void launch_decode_advance(long*, long*, int*, long*, int*, const long*,
                            const int*, int, int, int, hipStream_t);
 
@@ -256,6 +258,32 @@ void inv_cdf_sample(torch::Tensor out, torch::Tensor logits,
                         (int)logits.size(1), stream());
 }
 
+void sample_fused(torch::Tensor out, torch::Tensor logits,
+                  torch::Tensor temperature, torch::Tensor top_p,
+                  torch::Tensor top_k, torch::Tensor uniform) {
+  check(out, torch::kInt64, "out");
+  check(logits, torch::kBFloat16, "logits");
+  check(temperature, torch::kFloat32, "temperature");
+  check(top_p, torch::kFloat32, "top_p");
+  check(top_k, torch::kInt32, "top_k");
+  check(uniform, torch::kFloat32, "uniform");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0,
+              "logits must be [rows, vocab]");
+  const int64_t rows = logits.size(0);
+  TORCH_CHECK(logits.size(1) < (1LL << 30), "vocab too large");
+  TORCH_CHECK(out.numel() == rows && temperature.numel() == rows &&
+                  top_p.numel() == rows && top_k.numel() == rows &&
+                  uniform.numel() == rows,
+              "per-row tensors must have `rows` elements");
+  for (const torch::Tensor* t : {&out, &temperature, &top_p, &top_k, &uniform})
+    TORCH_CHECK(t->device() == logits.device(),
+                "sample_fused: tensors on different devices");
+  launch_sample_fused(out.data_ptr<long>(), cbf(logits),
+                      temperature.data_ptr<float>(), top_p.data_ptr<float>(),
+                      top_k.data_ptr<int>(), uniform.data_ptr<float>(), rows,
+                      (int)logits.size(1), stream());
+}
+
 void decode_advance(torch::Tensor input_ids, torch::Tensor positions,
                     torch::Tensor seq_lens, torch::Tensor slot_mapping,
                     torch::Tensor block_tables, torch::Tensor sampled_prev,
@@ -427,5 +455,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("silu_mul", &silu_mul);
   m.def("greedy_sample", &greedy_sample);
   m.def("inv_cdf_sample", &inv_cdf_sample);
+  m.def("sample_fused", &sample_fused);
   m.def("decode_advance", &decode_advance);
 }

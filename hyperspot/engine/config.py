@@ -129,6 +129,13 @@ class EngineConfig:
     # enqueue decode step n+1 before step n's tokens reach the host
     # (LLMEngine.step_pipelined); same tokens and finish reasons either way
     pipeline_decode: bool = True
+    # sample on the device with the fused top-k/top-p kernel
+    # (ops.sample_fused): stochastic rows then stay in the pipelined
+    # decode, whose graphs end in that kernel instead of the argmax.  Off
+    # by default: where tokens tie at a top-k/top-p cut, or a draw falls on
+    # a rounding boundary, it can pick another token than the sort-based
+    # ops.sample does for the same seed
+    device_sampling: bool = False
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,

@@ -98,12 +98,15 @@ class LLMEngine:
     # ---- pipelined stepping (depth one) ----
 
     def _pipe_eligible(self) -> bool:
-        """Every running row greedy and unguided: the next decode step's
+        """Every running row unguided, and greedy unless the device
+        samples (EngineConfig.device_sampling): the next decode step's
         inputs then depend on the in-flight tokens only through input_ids,
         which the device already holds."""
+        stochastic_ok = self.config.device_sampling
         for r in self.scheduler.running:
             sp = r.sampling
-            if sp.temperature != 0 or sp.response_schema is not None \
+            if (sp.temperature != 0 and not stochastic_ok) \
+                    or sp.response_schema is not None \
                     or sp.response_format in ("json", "tool_call"):
                 return False
         return True
@@ -116,7 +119,16 @@ class LLMEngine:
         reaches max_tokens in the in-flight step is left out of the next
         one; EOS / stop tokens are seen one step late, and the token of
         that extra step is dropped, so streams and finish reasons are
-        those of step()."""
+        those of step().
+
+        With device_sampling stochastic rows take the fast path too: the
+        graph's tail is sample_fused, fed one uniform per launched row.  A
+        row with `seed` draws from its own generator once per sampled
+        token in either path, so it gets the same tokens and finish reason
+        as from step() (the extra draw of a step launched past its EOS
+        comes after its last token).  Rows without a seed share one
+        generator, which that extra draw, and the order of draws, shift:
+        for them only the distribution is that of step()."""
         cfg = self.config
         sch = self.scheduler
         rn = self.runner

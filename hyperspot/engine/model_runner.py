@@ -143,9 +143,11 @@ class ModelRunner:
         self._pipe: Optional[dict] = None
         self._pipe_eager_io: Optional[dict] = None
         self._pipe_seq = 0
+        # With device_sampling a slot's control block is followed by one
+        # float32 uniform per row, so both go up in a single copy.
+        ctl_len = (5 if config.device_sampling else 4) * cap + 4
         self._pipe_ring = [
-            {"ctl": torch.empty(4 * cap + 4, dtype=torch.int32,
-                                pin_memory=pin),
+            {"ctl": torch.empty(ctl_len, dtype=torch.int32, pin_memory=pin),
              "tok": torch.empty(cap, dtype=torch.long, pin_memory=pin),
              "event": torch.cuda.Event() if pin else None}
             for _ in range(4)]
@@ -337,6 +339,8 @@ class ModelRunner:
         if not io["passthrough"]:
             # the graph's head kernel leaves host-filled inputs alone
             io["ctl"][4 * bucket:].fill_(-1)
+            if self.config.device_sampling:
+                io["temperature"].zero_()     # the tail is a plain argmax
             io["passthrough"] = True
         io["input_ids"][:B] = input_ids
         io["input_ids"][B:] = 0
@@ -371,10 +375,9 @@ class ModelRunner:
             # per-step control block of decode_advance (n_live < 0 =
             # pass-through, the synchronous path fills the inputs itself)
             "sampled": torch.zeros(bucket, dtype=torch.long, device=d),
-            "ctl": torch.full((4 * bucket + 4,), -1, dtype=torch.int32,
-                              device=d),
             "passthrough": True,
         }
+        io.update(self._pipe_ctl_io(bucket, d))
         meta = ForwardMeta(mode="decode", positions=io["positions"],
                            slot_mapping=io["slot_mapping"],
                            block_tables=io["block_tables"],
@@ -382,17 +385,17 @@ class ModelRunner:
         # warmup outside capture (allocator, hipBLASLt heuristics, RCCL)
         for _ in range(2):
             self._pipe_head(io)
-            ops.greedy_sample(
-                self.model(io["input_ids"], meta, self.kv_caches),
-                out=io["sampled"])
+            self._pipe_tail(
+                io, self.model(io["input_ids"], meta, self.kv_caches))
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, pool=self._graph_pool):
-            # head: per-step inputs derived on the device; tail: greedy
-            # argmax into the buffer the next replay's head reads
+            # head: per-step inputs derived on the device; tail: the
+            # sampled token (argmax, or sample_fused with device_sampling)
+            # into the buffer the next replay's head reads
             self._pipe_head(io)
             io["logits"] = self.model(io["input_ids"], meta, self.kv_caches)
-            ops.greedy_sample(io["logits"], out=io["sampled"])
+            self._pipe_tail(io, io["logits"])
         if self._graph_pool is None:
             self._graph_pool = g.pool()
         self._graphs[bucket] = g
@@ -419,7 +422,9 @@ class ModelRunner:
     # A decode step whose inputs do not depend on the tokens still in flight
     # is enqueued from lengths alone: decode_advance (head of the graph)
     # derives ids / positions / slots / table updates on the device from
-    # the previous step's argmax (tail of the graph).  Rows keep their slot
+    # the previous step's token (tail of the graph: the argmax, or with
+    # device_sampling sample_fused on per-row parameters uploaded at the
+    # re-seed and one uniform per row and step).  Rows keep their slot
     # in the bucket for as long as the device state lives; a row that leaves
     # becomes a padding row in place, and the state is re-seeded from the
     # host (every row on the host-id path, rows compacted) after any
@@ -429,6 +434,31 @@ class ModelRunner:
         ops.decode_advance(io["input_ids"], io["positions"], io["seq_lens"],
                            io["slot_mapping"], io["block_tables"],
                            io["sampled"], io["ctl"], self.config.block_size)
+
+    def _pipe_ctl_io(self, rows: int, d) -> dict:
+        """Device control block of a `rows`-row state.  With
+        device_sampling the per-row sampling parameters come with it, and
+        the uniforms sit right behind the block (one H2D for both)."""
+        if not self.config.device_sampling:
+            return {"ctl": torch.full((4 * rows + 4,), -1,
+                                      dtype=torch.int32, device=d)}
+        buf = torch.full((5 * rows + 4,), -1, dtype=torch.int32, device=d)
+        uni = buf[4 * rows + 4:].view(torch.float32)
+        uni.zero_()
+        return {
+            "ctl_uniform": buf, "ctl": buf[:4 * rows + 4], "uniform": uni,
+            # temperature 0 = argmax: padding rows, pass-through replays
+            "temperature": torch.zeros(rows, dtype=torch.float32, device=d),
+            "top_p": torch.ones(rows, dtype=torch.float32, device=d),
+            "top_k": torch.zeros(rows, dtype=torch.int32, device=d),
+        }
+
+    def _pipe_tail(self, io: dict, logits: torch.Tensor) -> None:
+        if self.config.device_sampling:
+            ops.sample_fused(logits, io["temperature"], io["top_p"],
+                             io["top_k"], io["uniform"], out=io["sampled"])
+        else:
+            ops.greedy_sample(logits, out=io["sampled"])
 
     def pipe_invalidate(self) -> None:
         self._pipe = None
@@ -481,12 +511,18 @@ class ModelRunner:
                                                 dtype=torch.int32, device=d),
                     "seq_lens": torch.ones(cap, dtype=torch.int32, device=d),
                     "sampled": torch.zeros(cap, dtype=torch.long, device=d),
-                    "ctl": torch.full((4 * cap + 4,), -1, dtype=torch.int32,
-                                      device=d),
                 }
+                full.update(self._pipe_ctl_io(cap, d))
             nrows = B
-            io = {k: v[:nrows] for k, v in full.items() if k != "ctl"}
-            io["ctl"] = full["ctl"][:4 * nrows + 4]
+            whole = ("ctl", "ctl_uniform", "uniform")
+            io = {k: v[:nrows] for k, v in full.items() if k not in whole}
+            if self.config.device_sampling:
+                buf = full["ctl_uniform"][:5 * nrows + 4]
+                io["ctl_uniform"] = buf
+                io["ctl"] = buf[:4 * nrows + 4]
+                io["uniform"] = buf[4 * nrows + 4:].view(torch.float32)
+            else:
+                io["ctl"] = full["ctl"][:4 * nrows + 4]
         self._pipe = {
             "graph": graph, "bucket": bucket, "io": io, "nrows": nrows,
             "reqs": list(reqs), "fresh": True,
@@ -499,6 +535,53 @@ class ModelRunner:
                 (r.sampling.max_tokens - r.num_generated for r in reqs),
                 dtype=np.int64, count=B),
         }
+        if self.config.device_sampling:
+            self._pipe_seed_sampling(reqs, io, nrows)
+
+    def _pipe_seed_sampling(self, reqs: List[Request], io: dict,
+                            nrows: int) -> None:
+        """Upload the rows' sampling parameters (once per re-seed; rows
+        past the live ones are argmax rows) and note which rows draw."""
+        import numpy as np
+        B = len(reqs)
+        par = torch.zeros(3, nrows, dtype=torch.float32)
+        par[1].fill_(1.0)
+        par[0, :B] = torch.tensor([r.sampling.temperature for r in reqs],
+                                  dtype=torch.float32)
+        par[1, :B] = torch.tensor([r.sampling.top_p for r in reqs],
+                                  dtype=torch.float32)
+        topk = torch.zeros(nrows, dtype=torch.int32)
+        topk[:B] = torch.tensor([r.sampling.top_k for r in reqs],
+                                dtype=torch.int32)
+        io["temperature"].copy_(par[0])
+        io["top_p"].copy_(par[1])
+        io["top_k"].copy_(topk)
+        p = self._pipe
+        p["stoch"] = par[0, :B].numpy() != 0
+        p["seeded"] = np.fromiter((r.sampling.seed is not None for r in reqs),
+                                  dtype=bool, count=B)
+
+    def _seed_gen_of(self, r: Request) -> torch.Generator:
+        g = getattr(r, "_seed_gen", None)
+        if g is None:
+            g = torch.Generator().manual_seed(r.sampling.seed)
+            r._seed_gen = g
+        return g
+
+    def _pipe_draw(self, p: dict, idx, uni: torch.Tensor) -> None:
+        """One uniform per launched row into the ring slot's pinned tail
+        (uni, float32 [nrows]): a seeded row takes one torch.rand(1) from
+        its own generator per sampled token, exactly as _sample does, the
+        others share self._gen."""
+        seeded = p["seeded"][idx]
+        plain = idx[~seeded]
+        if plain.size:
+            uni[torch.from_numpy(plain)] = torch.rand(
+                plain.size, generator=self._gen)
+        reqs = p["reqs"]
+        for i in idx[seeded]:
+            uni[int(i)] = torch.rand(
+                1, generator=self._seed_gen_of(reqs[i]))[0]
 
     @torch.inference_mode()
     def pipe_launch(self, seed_reqs: Optional[List[Request]] = None):
@@ -556,7 +639,14 @@ class ModelRunner:
             c[1][idx[boundary]] = bm.tables_np[rows[boundary],
                                                n[boundary] // bs]
         ctl[4 * R] = int(idx[-1]) + 1
-        io["ctl"].copy_(ring["ctl"][:4 * R + 4], non_blocking=nb)
+        if self.config.device_sampling and p["stoch"][idx].any():
+            # the step is certain to launch: only now consume the draws
+            self._pipe_draw(p, idx,
+                            ring["ctl"][4 * R + 4:5 * R + 4].view(
+                                torch.float32))
+            io["ctl_uniform"].copy_(ring["ctl"][:5 * R + 4], non_blocking=nb)
+        else:
+            io["ctl"].copy_(ring["ctl"][:4 * R + 4], non_blocking=nb)
         if p["graph"]:
             io["passthrough"] = False
             self._graphs[p["bucket"]].replay()
@@ -566,9 +656,8 @@ class ModelRunner:
                                slot_mapping=io["slot_mapping"],
                                block_tables=io["block_tables"],
                                seq_lens=io["seq_lens"])
-            ops.greedy_sample(
-                self.model(io["input_ids"], meta, self.kv_caches),
-                out=io["sampled"])
+            self._pipe_tail(
+                io, self.model(io["input_ids"], meta, self.kv_caches))
         # token D2H behind the step on the same stream, outside the graph
         ring["tok"][:R].copy_(io["sampled"], non_blocking=nb)
         if nb:
@@ -695,16 +784,17 @@ class ModelRunner:
             us = []
             for r in requests:
                 if r.sampling.seed is not None:
-                    g = getattr(r, "_seed_gen", None)
-                    if g is None:
-                        g = torch.Generator().manual_seed(r.sampling.seed)
-                        r._seed_gen = g
-                    us.append(torch.rand(1, generator=g))
+                    us.append(torch.rand(1, generator=self._seed_gen_of(r)))
                 else:
                     us.append(torch.rand(1, generator=self._gen))
             uniform = torch.cat(us)
         else:
             uniform = torch.rand(B, generator=self._gen)
         d = logits.device
+        if self.config.device_sampling:
+            # one kernel on the logits as they are (no fp32 copy, no sort);
+            # the pipelined step runs the same kernel on the same draws
+            return ops.sample_fused(logits, temps.to(d), top_p.to(d),
+                                    top_k.to(d), uniform.to(d)).cpu()
         return ops.sample(logits, temps.to(d), top_p.to(d), top_k.to(d),
                           uniform.to(d)).cpu()

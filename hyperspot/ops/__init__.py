@@ -366,6 +366,34 @@ def greedy_sample(logits: torch.Tensor,
     return res
 
 
+def sample_fused(logits: torch.Tensor, temperature: torch.Tensor,
+                 top_p: torch.Tensor, top_k: torch.Tensor,
+                 uniform: torch.Tensor,
+                 out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-row temperature / top-k / top-p sampling in one kernel
+    (csrc/sampling_fused.hip), straight from the bf16 logits: no fp32 copy,
+    no sort, no host decision, so it can be captured into a graph.
+
+    temperature, top_p float32 [rows]; top_k int32 [rows] (0 or >= vocab =
+    off); uniform float32 [rows] in [0, 1).  temperature == 0 rows take the
+    argmax.  Tokens of equal logit are kept or dropped together at either
+    cut (torch_ref.sample_fused spells the semantics out).  `out` (int64
+    [rows]) is written in place when given.  bf16 GPU logits go to the
+    kernel, anything else to the torch twin."""
+    if logits.is_cuda and logits.dtype == torch.bfloat16:
+        if out is None:
+            out = torch.empty(logits.shape[0], dtype=torch.long,
+                              device=logits.device)
+        _native().sample_fused(out, logits, temperature, top_p, top_k,
+                               uniform)
+        return out
+    res = torch_ref.sample_fused(logits, temperature, top_p, top_k, uniform)
+    if out is not None:
+        out.copy_(res)
+        return out
+    return res
+
+
 def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
                    seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
                    block_tables: torch.Tensor, sampled_prev: torch.Tensor,

@@ -228,6 +228,62 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor,
     return out
 
 
+def sample_fused(logits: torch.Tensor, temperature: torch.Tensor,
+                 top_p: torch.Tensor, top_k: torch.Tensor,
+                 uniform: torch.Tensor) -> torch.Tensor:
+    """Twin of csrc/sampling_fused.hip: tie-exact top-k / top-p sampling,
+    vectorised over rows, on whatever device the inputs are on.
+
+    x = logits, t = temperature, k = top_k, p = top_p, u = uniform:
+      t == 0          argmax.
+      0 < k < V       keep x >= the k-th largest x (ties at the cut stay).
+      weights         w = exp((x - max) / max(t, 1e-6)) over what is kept.
+      p < 1           keep a value's tokens while the mass strictly above
+                      that value is < p * sum(w); the maximum always stays.
+      draw            first kept token in vocabulary order whose inclusive
+                      running sum exceeds u * (kept mass); the last kept
+                      token with weight if rounding leaves none.
+    Tokens of equal value are kept or dropped together, so no sort order
+    enters the result.  Sums run in float64.
+    """
+    B, V = logits.shape
+    dev = logits.device
+    x = logits.double()
+    t = temperature.to(dev).double()
+    k = top_k.to(dev).long()
+    p = top_p.to(dev).double()
+    u = uniform.to(dev).double()
+    greedy = logits.float().argmax(-1)
+    xs, order = x.sort(-1, descending=True)
+    k_on = (k > 0) & (k < V)
+    kth = xs.gather(1, (torch.where(k_on, k, torch.ones_like(k)) - 1)[:, None])
+    keep = (x >= kth) | ~k_on[:, None]
+    m = xs[:, :1]
+    w = torch.exp((x - m) / t.clamp_min(1e-6)[:, None])
+    w = torch.where(keep & torch.isfinite(x), w, torch.zeros_like(w))
+    w = torch.nan_to_num(w, nan=0.0, posinf=0.0)
+    # mass strictly above each value: the exclusive running sum at the
+    # first sorted position of the value's tie group
+    ws = w.gather(1, order)
+    excl = ws.cumsum(-1) - ws
+    ar = torch.arange(V, device=dev).expand(B, V)
+    first = torch.ones(B, V, dtype=torch.bool, device=dev)
+    first[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    start = torch.where(first, ar, torch.zeros_like(ar)).cummax(-1).values
+    above = excl.gather(1, start)
+    z = ws.sum(-1, keepdim=True)
+    keep_s = (above < p[:, None] * z) | (start == 0) | (p >= 1)[:, None]
+    keep_p = torch.zeros_like(keep_s).scatter(1, order, keep_s)
+    w = torch.where(keep_p, w, torch.zeros_like(w))
+    c = w.cumsum(-1)
+    hit = c > (u * c[:, -1])[:, None]
+    tok = hit.int().argmax(-1)
+    last = (V - 1) - (w > 0).flip(-1).int().argmax(-1)
+    tok = torch.where(hit.any(-1), tok, last)
+    dead = ~(w > 0).any(-1)
+    return torch.where((temperature.to(dev) == 0) | dead, greedy, tok)
+
+
 def moe_route(hidden: torch.Tensor, router_w: torch.Tensor, top_k: int):
     """Softmax-topk routing: returns (weights [T,K], expert_ids [T,K])."""
     logits = hidden.float() @ router_w.float().t()

@@ -856,6 +856,10 @@ def main():
                     help="run chunked-prefill continuation / prefix-hit "
                          "steps on the MFMA flash kernel over the paged "
                          "cache (EngineConfig.prefill_paged_mfma)")
+    ap.add_argument("--device-sampling", action="store_true",
+                    help="sample top-k/top-p on the device at the decode "
+                         "graph's tail, so stochastic rows stay in the "
+                         "pipelined decode (EngineConfig.device_sampling)")
     args = ap.parse_args()
 
     logging.basicConfig(level=logging.INFO,
@@ -875,7 +879,8 @@ def main():
         num_gpu_blocks=args.num_gpu_blocks or None,
         enforce_eager=args.eager or not on_gpu, tp_size=args.tp,
         quant=args.quant, kv_dtype=args.kv_dtype,
-        prefill_paged_mfma=args.prefill_paged_mfma)
+        prefill_paged_mfma=args.prefill_paged_mfma,
+        device_sampling=args.device_sampling)
     rank = 0
     # MoE models shard experts over the same ranks as TP attention
     # (config 4: Mixtral EP over RCCL all-to-all).  Decode graphs stay ON
