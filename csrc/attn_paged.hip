@@ -407,6 +407,22 @@ __global__ __launch_bounds__(256) void paged_attn_v3_kernel(
         sc[wid][h][8 + t_loc] = p1;
       }
     }
+    // The one partial page of a row: slots >= nb hold whatever the page's
+    // last owner left there (the pool hands pages out unscrubbed).  The
+    // score select above masks their K, but a non-finite V byte times
+    // p == 0 is NaN, so zero those V rows as raw bits (0 is +0.0 in bf16
+    // and in e4m3fn).  nb is the same for the whole wave: full pages pay
+    // one branch, placed here where the V loads are awaited anyway (right
+    // after the loads it cost 3-9 %, profiles/r06_decode_poison.md).
+    if (nb < ATTN_BS) {
+      #pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (4 * g + i >= nb) {
+          if constexpr (KV8) vr2[i] = make_uint2(0u, 0u);
+          else vr4[i] = make_uint4(0u, 0u, 0u, 0u);
+        }
+      }
+    }
     // ---- PV: lane accumulates its dim slice over its 4 tokens ----
     float4 p4[GROUP];
     #pragma unroll
@@ -541,7 +557,10 @@ void launch_paged_attn(bf16* out, const bf16* q, const bf16* k_cache,
   // the same KV stream (the kvh=1 70B-TP8 shard: 2x a small KV re-read
   // buys the v3 structure + occupancy).  split>1 = flash-decode page
   // split with an fp32 partial workspace + merge kernel.
-  if (D == 128 && (group <= 4 || group == 8)) {
+  // Only the instantiated groups may enter: any other (group 3, say)
+  // falls through to the "unsupported" error below instead of matching
+  // no CASE3 and returning with `out` unwritten.
+  if (D == 128 && (group == 1 || group == 2 || group == 4 || group == 8)) {
     const int calls = (group == 8) ? 2 : 1;
     const int g = (group == 8) ? 4 : group;
     const int h_total = num_kv_heads * group;

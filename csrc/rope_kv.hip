@@ -13,8 +13,18 @@
 // q/k/v may be strided views into one fused qkv GEMM output buffer
 // (token stride qs/ks/vs in elements; head dim contiguous).
 // KV8: the paged cache stores OCP e4m3fn bytes (fp8 KV mode — halves the
-// decode-attention HBM stream; scale fixed at 1.0, k/v magnitudes sit in
-// the e4m3 normal range).
+// decode-attention HBM stream; scale fixed at 1.0).  k/v magnitudes
+// normally sit in the e4m3 normal range, but nothing upstream enforces it
+// and the hardware convert does not saturate: 464 still rounds to 448,
+// but 480, 1000, the bf16 maximum and +-Inf all came out as the NaN byte
+// on an MI355X, which then poisons every later read of the page.  So
+// values are clamped to +-448 (codes 0x7e/0xfe) before the convert;
+// torch_ref.kv_cache_append does the same.  What a NaN input becomes is
+// unspecified.
+DEV float sat_e4m3(float x) {
+  return __builtin_amdgcn_fmed3f(x, -448.f, 448.f);
+}
+
 template <int D, bool KV8>
 __global__ __launch_bounds__(256) void rope_kv_append_kernel(
     bf16* __restrict__ q, bf16* __restrict__ k, const bf16* __restrict__ v,
@@ -72,8 +82,10 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(
       if constexpr (KV8) {
         unsigned char* kc = reinterpret_cast<unsigned char*>(k_cache) +
             (((blk * KV + h) * block_size + off) * D);
-        unsigned plo = __builtin_amdgcn_cvt_pk_fp8_f32(r0, r1, 0u, false);
-        unsigned phi = __builtin_amdgcn_cvt_pk_fp8_f32(r2, r3, 0u, false);
+        unsigned plo = __builtin_amdgcn_cvt_pk_fp8_f32(
+            sat_e4m3(r0), sat_e4m3(r1), 0u, false);
+        unsigned phi = __builtin_amdgcn_cvt_pk_fp8_f32(
+            sat_e4m3(r2), sat_e4m3(r3), 0u, false);
         *reinterpret_cast<unsigned short*>(kc + j) = (unsigned short)plo;
         *reinterpret_cast<unsigned short*>(kc + HALF + j) =
             (unsigned short)phi;
@@ -92,15 +104,14 @@ __global__ __launch_bounds__(256) void rope_kv_append_kernel(
       const bf16* src = v + t * vs_stride + h * D + j;
       if constexpr (KV8) {
         bf16x8 vv = load_bf16x8(src);
+        float f[8];
+        #pragma unroll
+        for (int i = 0; i < 8; ++i) f[i] = sat_e4m3(bf16x8_get(vv, i));
         unsigned w0 = 0, w1 = 0;
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bf16x8_get(vv, 0),
-                                             bf16x8_get(vv, 1), w0, false);
-        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(bf16x8_get(vv, 2),
-                                             bf16x8_get(vv, 3), w0, true);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bf16x8_get(vv, 4),
-                                             bf16x8_get(vv, 5), w1, false);
-        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(bf16x8_get(vv, 6),
-                                             bf16x8_get(vv, 7), w1, true);
+        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w0, false);
+        w0 = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w0, true);
+        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], w1, false);
+        w1 = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], w1, true);
         uint2 pk{w0, w1};
         *reinterpret_cast<uint2*>(reinterpret_cast<unsigned char*>(v_cache)
             + (((blk * KV + h) * block_size + off) * D) + j) = pk;

@@ -63,10 +63,19 @@ def apply_rope(q: torch.Tensor, k: torch.Tensor, positions: torch.Tensor,
 def kv_cache_append(k: torch.Tensor, v: torch.Tensor,
                     k_cache: torch.Tensor, v_cache: torch.Tensor,
                     slot_mapping: torch.Tensor) -> None:
-    """Scatter k/v [T, KV, D] into paged caches [NB, KV, BS, D]."""
+    """Scatter k/v [T, KV, D] into paged caches [NB, KV, BS, D].
+
+    An e4m3fn cache saturates like csrc/rope_kv.hip: finite |x| > 448 and
+    +-Inf are stored as +-448, never as the NaN byte the plain torch
+    convert writes from 465 up.
+    """
     nb, kvh, bs, d = k_cache.shape
     blk = slot_mapping // bs
     off = slot_mapping % bs
+    if k_cache.dtype == torch.float8_e4m3fn:
+        k = k.float().clamp(-448.0, 448.0)
+    if v_cache.dtype == torch.float8_e4m3fn:
+        v = v.float().clamp(-448.0, 448.0)
     k_cache[blk, :, off] = k.to(k_cache.dtype)
     v_cache[blk, :, off] = v.to(v_cache.dtype)
 

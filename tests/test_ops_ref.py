@@ -81,6 +81,37 @@ def test_kv_append_and_paged_decode_match_dense_attention():
     assert torch.allclose(out[0], ref, atol=1e-5)
 
 
+def test_kv_append_fp8_cache_saturates_instead_of_nan():
+    """Same contract as csrc/rope_kv.hip: an e4m3fn cache stores finite
+    |x| > 448 and +-Inf as +-448 (codes 0x7e/0xfe), never as a NaN byte;
+    in-range values and bf16 caches are untouched by the clamp."""
+    big = [448.0, 464.0, 480.0, 1000.0,
+           torch.finfo(torch.bfloat16).max, float("inf")]
+    vals = torch.tensor(big + [-x for x in big] + [0.0, 1.5, -0.4375, 447.0])
+    # the plain convert is what must not reach the cache
+    assert vals.to(torch.float8_e4m3fn).float().isnan().any()
+    n, KV, BS, D = 1, 1, 4, vals.numel()
+    k = vals.view(n, KV, D).bfloat16()
+    v = k.flip(-1).contiguous()
+    kc = torch.zeros(2, KV, BS, D, dtype=torch.float8_e4m3fn)
+    vc = torch.zeros_like(kc)
+    R.kv_cache_append(k, v, kc, vc, torch.tensor([5]))
+    want = torch.tensor([0x7e] * 6 + [0xfe] * 6, dtype=torch.uint8)
+    got_k = kc.view(torch.uint8)[1, 0, 1]
+    got_v = vc.view(torch.uint8)[1, 0, 1].flip(-1)
+    assert torch.equal(got_k[:12], want) and torch.equal(got_v[:12], want)
+    tail = k[0, 0, 12:].float().to(torch.float8_e4m3fn).view(torch.uint8)
+    assert torch.equal(got_k[12:], tail) and torch.equal(got_v[12:], tail)
+    # every other slot stays as it was
+    kc.view(torch.uint8)[1, 0, 1] = 0
+    assert not kc.view(torch.uint8).any()
+    # a bf16 cache keeps the values as they are
+    kb = torch.zeros(2, KV, BS, D, dtype=torch.bfloat16)
+    vb = torch.zeros_like(kb)
+    R.kv_cache_append(k, v, kb, vb, torch.tensor([5]))
+    assert torch.equal(kb[1, 0, 1], k[0, 0])
+
+
 def test_prefill_attn_varlen_causal():
     torch.manual_seed(0)
     H, KV, D = 4, 2, 16

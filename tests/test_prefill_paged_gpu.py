@@ -288,11 +288,9 @@ def test_op_layer_dispatch(monkeypatch, rows, enabled, mfma):
                            for z, (_, n) in enumerate(cases)]).to(DEV),
         block_tables=c["bt"].to(DEV))
     q = c["q"].to(DEV)
-    # zeros instead of the NaN poison: the per-row kernel weighs the unused
-    # slots of a partly filled page with p = 0, which only finite bytes
-    # survive (the engine's pool starts zeroed)
-    kc = torch.nan_to_num(c["kc"], nan=0.0).to(DEV)
-    vc = torch.nan_to_num(c["vc"], nan=0.0).to(DEV)
+    # the poison stays in: the per-row kernel, too, must not let the unused
+    # slots of a partly filled page reach its result
+    kc, vc = c["kc"].to(DEV), c["vc"].to(DEV)
     out = ops.attention(q, None, None, kc, vc, meta, SCALE)
     assert ran == ["attn_prefill_paged_mfma" if mfma else "paged_attn"]
     _check(out.float().cpu(), c["ref"])
