@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Isolated kernel microbenchmarks (GPU only) — us/call + achieved GB/s.
 
-Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|sample|all]
+Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|sample|logprobs|all]
                                [--iters N]
 
 Shapes mirror the flagship bench (Llama-3-8B bf16, bs=256 ctx=512 decode):
@@ -287,6 +287,53 @@ def bench_sample(iters):
         del logits
 
 
+def bench_logprobs(iters, repeats=5):
+    """token_logprobs behind the sampler: every row asking for the chosen
+    token only (n_top 0), 5 and 20 alternatives, and no row asking (-1,
+    the launch floor), next to greedy_sample on the same logits, which
+    reads the row once.  Each case is timed `repeats` times, the cases
+    taking turns, and reported as the median with its range.  GB/s counts
+    one read of the bf16 logits, whatever the kernel really moves."""
+    import hyperspot.ops as ops
+    dev = "cuda:0"
+    vocab = 128256
+    for rows in (64, 512, 2048):
+        g = torch.Generator().manual_seed(rows)
+        logits = torch.empty(rows, vocab, dtype=torch.bfloat16, device=dev)
+        for r0 in range(0, rows, 256):          # bounded host memory
+            n = min(256, rows - r0)
+            logits[r0:r0 + n] = (torch.randn(n, vocab, generator=g) * 3).to(
+                torch.bfloat16).to(dev)
+        out = torch.empty(rows, dtype=torch.long, device=dev)
+        ops.greedy_sample(logits, out=out)
+        val = torch.empty(rows, 21, dtype=torch.float32, device=dev)
+        idx = torch.empty(rows, 21, dtype=torch.int32, device=dev)
+        nbytes = rows * vocab * 2
+
+        def lp_case(n):
+            n_top = torch.full((rows,), n, dtype=torch.int32, device=dev)
+            return lambda: ops.token_logprobs(logits, out, n_top, val, idx)
+
+        cases = [("greedy_sample", None,
+                  lambda: ops.greedy_sample(logits, out=out))]
+        cases += [("token_logprobs", n, lp_case(n)) for n in (-1, 0, 5, 20)]
+        times = {i: [] for i in range(len(cases))}
+        for rep in range(repeats):
+            for i, (_, _, fn) in enumerate(cases):
+                times[i].append(timed(fn, iters, warmup=20 if rep == 0 else 3))
+        base = sorted(times[0])[repeats // 2]
+        for i, (name, n, _) in enumerate(cases):
+            t = sorted(times[i])
+            us = t[repeats // 2]
+            print(json.dumps({
+                "kernel": name, "shape": f"{rows}x{vocab}", "n_top": n,
+                "us": round(us, 1), "us_min": round(t[0], 1),
+                "us_max": round(t[-1], 1),
+                "x_greedy": round(us / base, 2),
+                "GBps_logits": round(nbytes / us / 1e3, 0)}), flush=True)
+        del logits
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="attn")
@@ -303,6 +350,8 @@ def main():
         bench_prefill_paged(args.iters)
     if args.which in ("sample", "all"):
         bench_sample(args.iters)
+    if args.which in ("logprobs", "all"):
+        bench_logprobs(args.iters)
 
 
 if __name__ == "__main__":

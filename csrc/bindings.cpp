@@ -52,6 +52,8 @@ void launch_inv_cdf_sample(long*, const float*, const float*, long, int,
                            hipStream_t);
 void launch_sample_fused(long*, const bf16*, const float*, const float*,
                          const int*, const float*, long, int, hipStream_t);
+void launch_token_logprobs(float*, int*, const bf16*, const long*, const int*,
+                           long, int, hipStream_t);
 void launch_decode_advance(long*, long*, int*, long*, int*, const long*,
                            const int*, int, int, int, hipStream_t);
 
@@ -284,6 +286,36 @@ void sample_fused(torch::Tensor out, torch::Tensor logits,
                       (int)logits.size(1), stream());
 }
 
+// Chosen-token logprob and the n_top[r] most likely alternatives per row
+// (csrc/logprobs.hip).  n_top[r] < 0 leaves row r of the outputs untouched;
+// the contract is 0..20, larger values are clamped to 20 by the kernel.
+void token_logprobs(torch::Tensor out_val, torch::Tensor out_id,
+                    torch::Tensor logits, torch::Tensor chosen,
+                    torch::Tensor n_top) {
+  check(out_val, torch::kFloat32, "out_val");
+  check(out_id, torch::kInt32, "out_id");
+  check(logits, torch::kBFloat16, "logits");
+  check(chosen, torch::kInt64, "chosen");
+  check(n_top, torch::kInt32, "n_top");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) > 0,
+              "logits must be [rows, vocab]");
+  const int64_t rows = logits.size(0);
+  TORCH_CHECK(logits.size(1) < (1LL << 30), "vocab too large");
+  TORCH_CHECK(out_val.dim() == 2 && out_val.size(0) == rows &&
+                  out_val.size(1) == 21 && out_id.dim() == 2 &&
+                  out_id.size(0) == rows && out_id.size(1) == 21,
+              "out_val / out_id must be [rows, 21]");
+  TORCH_CHECK(chosen.numel() == rows && n_top.numel() == rows,
+              "per-row tensors must have `rows` elements");
+  for (const torch::Tensor* t : {&out_val, &out_id, &chosen, &n_top})
+    TORCH_CHECK(t->device() == logits.device(),
+                "token_logprobs: tensors on different devices");
+  launch_token_logprobs(out_val.data_ptr<float>(), out_id.data_ptr<int>(),
+                        cbf(logits), chosen.data_ptr<long>(),
+                        n_top.data_ptr<int>(), rows, (int)logits.size(1),
+                        stream());
+}
+
 void decode_advance(torch::Tensor input_ids, torch::Tensor positions,
                     torch::Tensor seq_lens, torch::Tensor slot_mapping,
                     torch::Tensor block_tables, torch::Tensor sampled_prev,
@@ -456,5 +488,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("greedy_sample", &greedy_sample);
   m.def("inv_cdf_sample", &inv_cdf_sample);
   m.def("sample_fused", &sample_fused);
+  m.def("token_logprobs", &token_logprobs);
   m.def("decode_advance", &decode_advance);
 }

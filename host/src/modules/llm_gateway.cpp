@@ -10,6 +10,7 @@
 
 #include <chrono>
 #include <cstring>
+#include <unordered_map>
 
 #include "../util/log.h"
 #include "system_modules.h"
@@ -224,6 +225,11 @@ void MuxClient::reader_loop() {
     const std::string ev = msg->at("event").as_string();
     if (ev == "batch") {
       const Json& items = msg->at("items");
+      // "lp": [[rid, lp_chosen, [id, ...], [lp, ...]], ...] — present only
+      // when a row of this step asked for logprobs
+      std::unordered_map<std::string, const Json*> lps;
+      if (msg->at("lp").is_array())
+        for (auto& e : msg->at("lp").arr()) lps[e.at(0).as_string()] = &e;
       std::lock_guard<std::mutex> lk(mu_);
       for (auto& it : items.arr()) {
         // [rid, token_id] delta | [rid, tok, fin, in, out] final —
@@ -242,6 +248,24 @@ void MuxClient::reader_loop() {
           d["event"] = "delta";
           d["token_id"] = (long)tok;
           d["text"] = text;
+          auto lp = lps.find(rid);
+          if (lp != lps.end()) {
+            const Json& e = *lp->second;
+            Json top = Json::array();
+            const Json& ids = e.at(2);
+            const Json& vals = e.at(3);
+            for (size_t k = 0; k < ids.size() && k < vals.size(); ++k) {
+              Json pair = Json::array();
+              pair.push_back(ids.at(k));
+              pair.push_back(vals.at(k));
+              top.push_back(std::move(pair));
+            }
+            Json rec = Json::object();
+            rec["token_id"] = (long)tok;
+            rec["logprob"] = e.at(1);
+            rec["top"] = std::move(top);
+            d["logprob"] = std::move(rec);
+          }
           s.q.push_back(std::move(d));
           if (fin) {
             Json u = Json::object();
@@ -606,6 +630,11 @@ void LlmGatewayModule::spawn_one(Worker& wk) {
         args.push_back("--kv-dtype");
         args.push_back(worker_cfg_.at("kv_dtype").as_string());
       }
+      // the two only pay off together for stochastic rows
+      if (worker_cfg_.at("device_sampling").as_bool(false))
+        args.push_back("--device-sampling");
+      if (worker_cfg_.at("device_logprobs").as_bool(false))
+        args.push_back("--device-logprobs");
     }
     std::vector<char*> argv;
     for (auto& a : args) argv.push_back(const_cast<char*>(a.c_str()));
@@ -763,6 +792,64 @@ void LlmGatewayModule::record_usage(const std::string& tenant,
   u.requests += 1;
 }
 
+// ---- logprobs (OpenAI-style `logprobs` / `top_logprobs`) ----
+
+// 400 unless `top_logprobs` is an integer in 0..20 given with
+// `logprobs: true`
+static void validate_logprobs(const Json& body) {
+  const Json& on = body.at("logprobs");
+  const Json& top = body.at("top_logprobs");
+  if (!on.is_null() && !on.is_bool())
+    throw Problem{400, "Bad Request", "about:blank",
+                  "'logprobs' must be a boolean", "validation_error"};
+  if (top.is_null()) return;
+  const double t = top.as_number(-1);
+  if (!top.is_number() || t != (double)(long)t || t < 0 || t > 20)
+    throw Problem{400, "Bad Request", "about:blank",
+                  "'top_logprobs' must be an integer in 0..20",
+                  "validation_error"};
+  if (!on.as_bool(false))
+    throw Problem{400, "Bad Request", "about:blank",
+                  "'top_logprobs' requires 'logprobs': true",
+                  "validation_error"};
+}
+
+// forward both fields to the worker; true when the request asks
+static bool forward_logprobs(const Json& body, Json& params) {
+  for (const char* f : {"logprobs", "top_logprobs"})
+    if (body.contains(f)) params[f] = body.at(f);
+  return params.at("logprobs").as_bool(false);
+}
+
+// {"token","token_id","bytes","logprob"} of the byte tokenizer: ids 4..259
+// are the bytes 0..255, everything else is a special token without bytes
+static Json logprob_token(long id, double lp) {
+  Json bytes = Json::array();
+  std::string tok;
+  if (id >= 4 && id < 260) {
+    bytes.push_back(id - 4);
+    if (id - 4 < 0x80) tok.assign(1, static_cast<char>(id - 4));
+  }
+  Json t = Json::object();
+  t["token"] = tok;
+  t["token_id"] = id;
+  t["bytes"] = bytes;
+  t["logprob"] = lp;
+  return t;
+}
+
+// response entry from a worker record {"token_id","logprob","top":[[id,lp]]}
+static Json logprob_entry(const Json& rec) {
+  Json e = logprob_token(rec.at("token_id").as_int(0),
+                         rec.at("logprob").as_number(0));
+  Json top = Json::array();
+  if (rec.at("top").is_array())
+    for (auto& p : rec.at("top").arr())
+      top.push_back(logprob_token(p.at(0).as_int(0), p.at(1).as_number(0)));
+  e["top_logprobs"] = std::move(top);
+  return e;
+}
+
 Json LlmGatewayModule::run_chat_blocking(const Json& body,
                                          const Json& resolved,
                                          const std::string& rid) {
@@ -783,6 +870,7 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
   for (const char* f : {"temperature", "top_p", "top_k", "max_tokens",
                         "seed", "ignore_eos", "response_format"})
     if (body.contains(f)) params[f] = body.at(f);
+  const bool want_lp = forward_logprobs(body, params);
   // reference request schema: `response_schema` asks for structured
   // output — the engine enforces the JSON grammar via constrained
   // decoding (engine/guided.py); the schema body itself is advisory
@@ -826,6 +914,7 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
       continue;
     }
     std::string text;
+    Json lp_content = Json::array();
     Json usage;
     std::string finish = "stop";
     bool first = true;
@@ -859,7 +948,12 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
                       "provider_timeout"};
       }
       const std::string ev = msg->at("event").as_string();
-      if (ev == "delta") { first = false; text += msg->at("text").as_string(); }
+      if (ev == "delta") {
+        first = false;
+        text += msg->at("text").as_string();
+        if (want_lp && msg->contains("logprob"))
+          lp_content.push_back(logprob_entry(msg->at("logprob")));
+      }
       else if (ev == "done") {
         usage = msg->at("usage");
         finish = msg->at("finish_reason").as_string("stop");
@@ -912,6 +1006,12 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
     resp["model_used"] = resolved.at("canonical_id").as_string();
     resp["fallback_used"] = false;
     resp["finish_reason"] = finish;
+    if (want_lp) {
+      // one entry per generated token
+      Json lp = Json::object();
+      lp["content"] = std::move(lp_content);
+      resp["logprobs"] = std::move(lp);
+    }
     return resp;
   }
   throw Problem{503, "Service Unavailable", "about:blank",
@@ -923,11 +1023,13 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
 static std::string sse_chunk(const std::string& id, const std::string& model,
                              const Json& delta,
                              const std::string& finish_reason = "",
-                             const Json& usage = Json()) {
+                             const Json& usage = Json(),
+                             const Json& logprobs = Json()) {
   Json c = Json::object();
   c["id"] = id;
   c["model"] = model;
   c["delta"] = delta;
+  if (!logprobs.is_null()) c["logprobs"] = logprobs;
   if (!finish_reason.empty()) c["finish_reason"] = finish_reason;
   if (!usage.is_null()) c["usage"] = usage;
   return "data: " + c.dump() + "\n\n";
@@ -1003,6 +1105,7 @@ void LlmGatewayModule::chat_handler(HttpRequest& req, ResponseWriter& w) {
                   "'model' and non-empty 'messages' are required",
                   "validation_error"};
   const bool stream = body.at("stream").as_bool(false);
+  validate_logprobs(body);
 
   SecurityContext sec =
       SecurityContext::from_json(req.extensions.at("security"));
@@ -1111,6 +1214,7 @@ void LlmGatewayModule::chat_handler(HttpRequest& req, ResponseWriter& w) {
   for (const char* f : {"temperature", "top_p", "top_k", "max_tokens",
                         "seed", "ignore_eos", "response_format"})
     if (body.contains(f)) params[f] = body.at(f);
+  const bool want_lp = forward_logprobs(body, params);
   // reference request schema: `response_schema` asks for structured
   // output — the engine enforces the JSON grammar via constrained
   // decoding (engine/guided.py); the schema body itself is advisory
@@ -1228,7 +1332,14 @@ void LlmGatewayModule::chat_handler(HttpRequest& req, ResponseWriter& w) {
       Json d = Json::object();
       d["content"] = msg->at("text").as_string();
       if (forced_tool) acc_text += msg->at("text").as_string();
-      if (!w.write_chunk(sse_chunk(rid, canonical, d))) {
+      Json lp;                 // {"content": [entry]} beside the delta
+      if (want_lp && msg->contains("logprob")) {
+        Json one = Json::array();
+        one.push_back(logprob_entry(msg->at("logprob")));
+        lp = Json::object();
+        lp["content"] = std::move(one);
+      }
+      if (!w.write_chunk(sse_chunk(rid, canonical, d, "", Json(), lp))) {
         client_gone = true;    // abort generation server-side
         mux->abort(rid);
         break;
@@ -1552,6 +1663,12 @@ void LlmGatewayModule::register_rest(ModuleCtx& ctx, RestRegistry& rest) {
     Json i = Json::object(); i["type"] = "integer";
     props["top_k"] = i;
     props["max_tokens"] = i;
+    props["logprobs"] = b;
+    Json tl = Json::object();
+    tl["type"] = "integer";
+    tl["minimum"] = (long)0;
+    tl["maximum"] = (long)20;
+    props["top_logprobs"] = tl;
     req_schema["properties"] = props;
     Json required = Json::array();
     required.push_back("model");

@@ -136,6 +136,12 @@ class EngineConfig:
     # a rounding boundary, it can pick another token than the sort-based
     # ops.sample does for the same seed
     device_sampling: bool = False
+    # keep rows that ask for logprobs (SamplingParams.logprobs) in the
+    # pipelined decode: every decode graph then ends in ops.token_logprobs
+    # behind the sampler, and the records ride the staging ring.  Off by
+    # default, so that the default graphs launch what they always did;
+    # logprob rows then take the synchronous step
+    device_logprobs: bool = False
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,
@@ -178,6 +184,11 @@ class SamplingParams:
     # declared tool names: a forced tool call ("tool_call" format)
     # narrows the emitted name to one of these (guided.ToolCallMachine)
     tool_names: tuple = ()
+    # per-token log-probabilities: None = off, 0 = the sampled token only,
+    # 1..20 = plus that many most likely alternatives.  The distribution
+    # is the one the token was chosen from at temperature 1, before top-k
+    # and top-p (after the guided-decoding mask)
+    logprobs: Optional[int] = None
 
     @property
     def greedy(self) -> bool:

@@ -40,6 +40,10 @@ class LLMEngine:
                     request_id: Optional[str] = None,
                     tenant_id: str = "default") -> str:
         rid = request_id or f"req-{next(self._id_counter)}"
+        lp = sampling.logprobs if sampling is not None else None
+        if lp is not None and not (isinstance(lp, int) and 0 <= lp <= 20):
+            raise ValueError(
+                f"SamplingParams.logprobs must be None or 0..20, got {lp!r}")
         req = Request(request_id=rid,
                       prompt_token_ids=list(prompt_token_ids),
                       sampling=sampling or SamplingParams(),
@@ -81,7 +85,8 @@ class LLMEngine:
         # next pipelined step re-seeds the device state
         self.runner.pipe_invalidate()
         bm = self.runner.block_manager
-        for req, tok in zip(batch.requests, tokens.tolist()):
+        lps = self.runner.last_logprobs
+        for i, (req, tok) in enumerate(zip(batch.requests, tokens.tolist())):
             if batch.mode == "prefill" and bm.enable_prefix_caching:
                 # the chunk's full prompt blocks are now computed and
                 # shareable with later prompts
@@ -91,21 +96,25 @@ class LLMEngine:
                 continue     # mid-prompt chunk: no token is sampled yet
             req.append_output(int(tok), self.eos_token_id)
             outputs.append(StepOutput(req.request_id, int(tok), req.finished,
-                                      req.finish_reason))
+                                      req.finish_reason,
+                                      lps[i] if lps is not None else None))
         self.scheduler.finish_step()
         return outputs
 
     # ---- pipelined stepping (depth one) ----
 
     def _pipe_eligible(self) -> bool:
-        """Every running row unguided, and greedy unless the device
-        samples (EngineConfig.device_sampling): the next decode step's
-        inputs then depend on the in-flight tokens only through input_ids,
-        which the device already holds."""
+        """Every running row unguided, greedy unless the device samples
+        (EngineConfig.device_sampling), and without logprobs unless the
+        decode graphs compute them (EngineConfig.device_logprobs): the
+        next decode step's inputs then depend on the in-flight tokens only
+        through input_ids, which the device already holds."""
         stochastic_ok = self.config.device_sampling
+        logprobs_ok = self.config.device_logprobs
         for r in self.scheduler.running:
             sp = r.sampling
             if (sp.temperature != 0 and not stochastic_ok) \
+                    or (sp.logprobs is not None and not logprobs_ok) \
                     or sp.response_schema is not None \
                     or sp.response_format in ("json", "tool_call"):
                 return False
@@ -159,12 +168,17 @@ class LLMEngine:
         outputs: List[StepOutput] = []
         done = []
         eos = self.eos_token_id
-        for req, tok in self.runner.pipe_collect(h):
+        pairs = self.runner.pipe_collect(h)
+        lps = h.records
+        for i, (req, tok) in enumerate(pairs):
             if req.finished:
-                continue   # stopped one step earlier, or aborted: dropped
+                # stopped one step earlier, or aborted: dropped, with its
+                # logprob record
+                continue
             req.append_output(tok, eos)
             outputs.append(StepOutput(req.request_id, tok, req.finished,
-                                      req.finish_reason))
+                                      req.finish_reason,
+                                      lps[i] if lps is not None else None))
             if req.finished:
                 done.append(req)
         bm = self.runner.block_manager

@@ -22,7 +22,7 @@ from hyperspot.models.llama import ForwardMeta
 from .config import EngineConfig
 from .kv_cache import (BlockManager, allocate_kv_caches,
                        compute_num_gpu_blocks)
-from .request import Request
+from .request import Request, TokenLogprobs
 from .scheduler import ScheduledBatch
 
 log = logging.getLogger(__name__)
@@ -59,12 +59,32 @@ def _load_tunableop_results() -> None:
         log.warning("TunableOp load failed: %s", e)
 
 
+def _logprob_records(val, idx, n_top) -> List[Optional[TokenLogprobs]]:
+    """Host records from ops.token_logprobs' outputs (numpy [rows, 21]);
+    n_top[i] < 0 = row i did not ask."""
+    ninf = float("-inf")
+    out: List[Optional[TokenLogprobs]] = []
+    for i, n in enumerate(n_top):
+        if n < 0:
+            out.append(None)
+            continue
+        ids = idx[i, 1:1 + n].tolist()
+        vals = val[i, 1:1 + n].tolist()
+        out.append(TokenLogprobs(
+            int(idx[i, 0]), float(val[i, 0]),
+            [(t, v) for t, v in zip(ids, vals) if v > ninf]))
+    return out
+
+
 class PipeStep:
     """One enqueued pipelined decode step: the rows it runs (slot order),
     the staging slot its tokens land in, and the sequences whose pages may
-    only be freed once it has been collected."""
+    only be freed once it has been collected.  lp_n: logprobs asked per
+    launched row (None = the step copied no logprob records back);
+    records: what pipe_collect made of them."""
 
-    __slots__ = ("reqs", "slots", "ring", "deferred_free", "_rids")
+    __slots__ = ("reqs", "slots", "ring", "deferred_free", "_rids", "lp_n",
+                 "records")
 
     def __init__(self, reqs, slots, ring):
         self.reqs = reqs
@@ -72,6 +92,8 @@ class PipeStep:
         self.ring = ring
         self.deferred_free: List[str] = []
         self._rids = None
+        self.lp_n = None
+        self.records = None
 
     def runs(self, request_id: str) -> bool:
         if self._rids is None:
@@ -151,6 +173,16 @@ class ModelRunner:
              "tok": torch.empty(cap, dtype=torch.long, pin_memory=pin),
              "event": torch.cuda.Event() if pin else None}
             for _ in range(4)]
+        if config.device_logprobs:
+            cols = ops.torch_ref.LOGPROB_COLS
+            for slot in self._pipe_ring:
+                slot["lp_val"] = torch.empty(cap, cols, dtype=torch.float32,
+                                             pin_memory=pin)
+                slot["lp_id"] = torch.empty(cap, cols, dtype=torch.int32,
+                                            pin_memory=pin)
+        # logprob records of the last execute(), one per batch row (None =
+        # the row did not ask), or None when no row asked
+        self.last_logprobs: Optional[List[Optional[TokenLogprobs]]] = None
 
     # ---------------- input preparation ----------------
 
@@ -341,6 +373,8 @@ class ModelRunner:
             io["ctl"][4 * bucket:].fill_(-1)
             if self.config.device_sampling:
                 io["temperature"].zero_()     # the tail is a plain argmax
+            if self.config.device_logprobs:
+                io["lp_n"].fill_(-1)          # and computes no logprobs
             io["passthrough"] = True
         io["input_ids"][:B] = input_ids
         io["input_ids"][B:] = 0
@@ -439,19 +473,31 @@ class ModelRunner:
         """Device control block of a `rows`-row state.  With
         device_sampling the per-row sampling parameters come with it, and
         the uniforms sit right behind the block (one H2D for both)."""
+        io = {}
+        if self.config.device_logprobs:
+            cols = ops.torch_ref.LOGPROB_COLS
+            # lp_n -1 = the row asks for none: padding rows, pass-through
+            # replays, rows without SamplingParams.logprobs
+            io["lp_n"] = torch.full((rows,), -1, dtype=torch.int32, device=d)
+            io["lp_val"] = torch.full((rows, cols), float("-inf"),
+                                      dtype=torch.float32, device=d)
+            io["lp_id"] = torch.full((rows, cols), -1, dtype=torch.int32,
+                                     device=d)
         if not self.config.device_sampling:
-            return {"ctl": torch.full((4 * rows + 4,), -1,
-                                      dtype=torch.int32, device=d)}
+            io["ctl"] = torch.full((4 * rows + 4,), -1, dtype=torch.int32,
+                                   device=d)
+            return io
         buf = torch.full((5 * rows + 4,), -1, dtype=torch.int32, device=d)
         uni = buf[4 * rows + 4:].view(torch.float32)
         uni.zero_()
-        return {
+        io.update({
             "ctl_uniform": buf, "ctl": buf[:4 * rows + 4], "uniform": uni,
             # temperature 0 = argmax: padding rows, pass-through replays
             "temperature": torch.zeros(rows, dtype=torch.float32, device=d),
             "top_p": torch.ones(rows, dtype=torch.float32, device=d),
             "top_k": torch.zeros(rows, dtype=torch.int32, device=d),
-        }
+        })
+        return io
 
     def _pipe_tail(self, io: dict, logits: torch.Tensor) -> None:
         if self.config.device_sampling:
@@ -459,6 +505,9 @@ class ModelRunner:
                              io["top_k"], io["uniform"], out=io["sampled"])
         else:
             ops.greedy_sample(logits, out=io["sampled"])
+        if self.config.device_logprobs:
+            ops.token_logprobs(logits, io["sampled"], io["lp_n"],
+                               io["lp_val"], io["lp_id"])
 
     def pipe_invalidate(self) -> None:
         self._pipe = None
@@ -537,6 +586,14 @@ class ModelRunner:
         }
         if self.config.device_sampling:
             self._pipe_seed_sampling(reqs, io, nrows)
+        if self.config.device_logprobs:
+            # once per re-seed; rows past the live ones ask for none
+            lp = torch.full((nrows,), -1, dtype=torch.int32)
+            lp[:B] = torch.tensor(
+                [-1 if r.sampling.logprobs is None else r.sampling.logprobs
+                 for r in reqs], dtype=torch.int32)
+            io["lp_n"].copy_(lp)
+            self._pipe["lp_n"] = lp[:B].numpy()
 
     def _pipe_seed_sampling(self, reqs: List[Request], io: dict,
                             nrows: int) -> None:
@@ -660,18 +717,30 @@ class ModelRunner:
                 io, self.model(io["input_ids"], meta, self.kv_caches))
         # token D2H behind the step on the same stream, outside the graph
         ring["tok"][:R].copy_(io["sampled"], non_blocking=nb)
+        step = PipeStep([p["reqs"][i] for i in idx], idx, ring)
+        if self.config.device_logprobs and (p["lp_n"][idx] >= 0).any():
+            # the records follow the tokens, only when a launched row asks
+            ring["lp_val"][:R].copy_(io["lp_val"], non_blocking=nb)
+            ring["lp_id"][:R].copy_(io["lp_id"], non_blocking=nb)
+            step.lp_n = p["lp_n"][idx]
         if nb:
             ring["event"].record()
         p["remaining"][idx] -= 1
-        return PipeStep([p["reqs"][i] for i in idx], idx, ring)
+        return step
 
     def pipe_collect(self, step: "PipeStep"):
         """Wait for the step's tokens (its own event, never a device-wide
-        sync); returns [(request, token_id)] in slot order."""
+        sync); returns [(request, token_id)] in slot order.  The logprob
+        records of the same rows, if the step carries any, are left in
+        step.records."""
         ev = step.ring["event"]
         if ev is not None:
             ev.synchronize()
         toks = step.ring["tok"].numpy()[step.slots].tolist()
+        if step.lp_n is not None:
+            step.records = _logprob_records(
+                step.ring["lp_val"].numpy()[step.slots],
+                step.ring["lp_id"].numpy()[step.slots], step.lp_n.tolist())
         return zip(step.reqs, toks)
 
     # ---------------- embeddings ----------------
@@ -769,12 +838,29 @@ class ModelRunner:
         logits[gidx, :NB] += small.to(device=d, dtype=logits.dtype)
 
     def _sample(self, logits: torch.Tensor, requests: List[Request]) -> torch.Tensor:
-        B = logits.shape[0]
         self._apply_guided(logits, requests)
+        tokens = self._sample_tokens(logits, requests)
+        # after the token is chosen, on the (guided-masked) logits it was
+        # chosen from; the records wait in last_logprobs for LLMEngine.step
+        n_top = [-1 if r.sampling.logprobs is None else r.sampling.logprobs
+                 for r in requests]
+        self.last_logprobs = None
+        if max(n_top) >= 0:
+            d = logits.device
+            val, idx = ops.token_logprobs(
+                logits, tokens.to(d),
+                torch.tensor(n_top, dtype=torch.int32).to(d))
+            self.last_logprobs = _logprob_records(
+                val.cpu().numpy(), idx.cpu().numpy(), n_top)
+        return tokens.cpu()
+
+    def _sample_tokens(self, logits: torch.Tensor,
+                       requests: List[Request]) -> torch.Tensor:
+        B = logits.shape[0]
         temps = torch.tensor([r.sampling.temperature for r in requests],
                              dtype=torch.float32)
         if bool((temps == 0).all()):
-            return ops.greedy_sample(logits).cpu()
+            return ops.greedy_sample(logits)
         top_p = torch.tensor([r.sampling.top_p for r in requests],
                              dtype=torch.float32)
         top_k = torch.tensor([r.sampling.top_k for r in requests],
@@ -795,6 +881,6 @@ class ModelRunner:
             # one kernel on the logits as they are (no fp32 copy, no sort);
             # the pipelined step runs the same kernel on the same draws
             return ops.sample_fused(logits, temps.to(d), top_p.to(d),
-                                    top_k.to(d), uniform.to(d)).cpu()
+                                    top_k.to(d), uniform.to(d))
         return ops.sample(logits, temps.to(d), top_p.to(d), top_k.to(d),
-                          uniform.to(d)).cpu()
+                          uniform.to(d))

@@ -5,7 +5,7 @@ from __future__ import annotations
 import enum
 import time
 from dataclasses import dataclass, field
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 from .config import SamplingParams
 
@@ -82,8 +82,21 @@ class Request:
 
 
 @dataclass
+class TokenLogprobs:
+    """Log-probability record of one generated token: the token itself and
+    the most likely alternatives as (token id, logprob), most likely first.
+    `top` holds finite entries only (a guided row with three legal tokens
+    and logprobs=5 carries three)."""
+
+    token_id: int
+    logprob: float
+    top: List[Tuple[int, float]] = field(default_factory=list)
+
+
+@dataclass
 class StepOutput:
     request_id: str
     token_id: int
     finished: bool
     finish_reason: Optional[FinishReason]
+    logprobs: Optional[TokenLogprobs] = None

@@ -394,6 +394,36 @@ def sample_fused(logits: torch.Tensor, temperature: torch.Tensor,
     return res
 
 
+def token_logprobs(logits: torch.Tensor, chosen: torch.Tensor,
+                   n_top: torch.Tensor, out_val: torch.Tensor | None = None,
+                   out_id: torch.Tensor | None = None):
+    """Log-probability of each row's chosen token and of its n_top[r] most
+    likely tokens, in one kernel (csrc/logprobs.hip) straight from the bf16
+    logits: no fp32 copy, no sort, no host decision, so it can be captured
+    into a graph behind the sampler.
+
+    chosen int64 [rows]; n_top int32 [rows]: < 0 = the row did not ask (its
+    outputs stay untouched), 0 = the chosen token only, 1..20 = plus that
+    many alternatives (values above 20 are outside the contract).  Returns
+    (val float32 [rows, 21], id int32 [rows, 21]); column 0 is the chosen
+    token, columns 1..n the alternatives by (-logit, id), the rest
+    (-inf, -1).  torch_ref.token_logprobs spells the semantics out.
+    `out_val` / `out_id` are written in place when given.  bf16 GPU logits
+    go to the kernel, anything else to the torch twin."""
+    if logits.is_cuda and logits.dtype == torch.bfloat16:
+        rows = logits.shape[0]
+        if out_val is None:
+            out_val = torch.full((rows, torch_ref.LOGPROB_COLS),
+                                 float("-inf"), dtype=torch.float32,
+                                 device=logits.device)
+        if out_id is None:
+            out_id = torch.full((rows, torch_ref.LOGPROB_COLS), -1,
+                                dtype=torch.int32, device=logits.device)
+        _native().token_logprobs(out_val, out_id, logits, chosen, n_top)
+        return out_val, out_id
+    return torch_ref.token_logprobs(logits, chosen, n_top, out_val, out_id)
+
+
 def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
                    seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
                    block_tables: torch.Tensor, sampled_prev: torch.Tensor,

@@ -293,6 +293,65 @@ def sample_fused(logits: torch.Tensor, temperature: torch.Tensor,
     return torch.where((temperature.to(dev) == 0) | dead, greedy, tok)
 
 
+LOGPROB_COLS = 21       # the chosen token + up to 20 alternatives
+
+
+def token_logprobs(logits: torch.Tensor, chosen: torch.Tensor,
+                   n_top: torch.Tensor, out_val: torch.Tensor = None,
+                   out_id: torch.Tensor = None):
+    """Twin of csrc/logprobs.hip, vectorised over rows.
+
+    logits [B, V]; chosen int64 [B]; n_top int32 [B].  Returns (val float32
+    [B, 21], id int32 [B, 21]).  Per row, with n = min(n_top, 20):
+      n_top < 0    the row did not ask: its outputs are left as they are
+                   (fresh outputs hold id -1, value -inf).
+      column 0     (chosen, logprob of chosen); -inf when chosen lies
+                   outside [0, V) or on a non-finite logit.
+      columns 1..n the first n tokens of a stable sort by (-logit, id).
+      the rest     id -1, value -inf.
+    logprob = x - logsumexp over the finite logits of the row as handed in
+    (temperature 1, before top-k / top-p); non-finite logits weigh nothing,
+    rank below every finite one and report -inf.  Sums run in float64.
+    """
+    B, V = logits.shape
+    dev = logits.device
+    ninf = float("-inf")
+    if out_val is None:
+        out_val = torch.full((B, LOGPROB_COLS), ninf, dtype=torch.float32,
+                             device=dev)
+    if out_id is None:
+        out_id = torch.full((B, LOGPROB_COLS), -1, dtype=torch.int32,
+                            device=dev)
+    n = n_top.to(dev).long()
+    ask = n >= 0
+    if not bool(ask.any()):
+        return out_val, out_id
+    x = logits.double()
+    fin = torch.isfinite(x)
+    xf = torch.where(fin, x, torch.full_like(x, ninf))
+    m = xf.max(-1, keepdim=True).values
+    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
+    lse = m + torch.log(torch.exp(xf - m).sum(-1, keepdim=True))
+    lp = torch.where(fin, x - lse, torch.full_like(x, ninf))
+    K = min(LOGPROB_COLS - 1, V)
+    order = torch.sort(-xf, dim=-1, stable=True).indices[:, :K]
+    valid = torch.arange(K, device=dev)[None, :] < n.clamp(max=K)[:, None]
+    val = torch.full((B, LOGPROB_COLS), ninf, dtype=torch.float64,
+                     device=dev)
+    idx = torch.full((B, LOGPROB_COLS), -1, dtype=torch.long, device=dev)
+    val[:, 1:1 + K] = torch.where(valid, lp.gather(1, order),
+                                  val[:, 1:1 + K])
+    idx[:, 1:1 + K] = torch.where(valid, order, idx[:, 1:1 + K])
+    c = chosen.to(dev).long()
+    ok = (c >= 0) & (c < V)
+    lpc = lp.gather(1, c.clamp(0, V - 1)[:, None]).squeeze(1)
+    val[:, 0] = torch.where(ok, lpc, torch.full_like(lpc, ninf))
+    idx[:, 0] = c
+    out_val.copy_(torch.where(ask[:, None], val.to(out_val.dtype), out_val))
+    out_id.copy_(torch.where(ask[:, None], idx.to(out_id.dtype), out_id))
+    return out_val, out_id
+
+
 def moe_route(hidden: torch.Tensor, router_w: torch.Tensor, top_k: int):
     """Softmax-topk routing: returns (weights [T,K], expert_ids [T,K])."""
     logits = hidden.float() @ router_w.float().t()

@@ -221,12 +221,27 @@ class HyperspotClient:
         body = {"model": self._model(model),
                 "messages": self._norm_messages(messages),
                 "stream": True, **params}
+        for ev in self._chat_events(body):
+            delta = ev.get("delta", {})
+            if delta.get("content"):
+                yield delta["content"]
+
+    def chat_stream_events(self, messages: List[Dict[str, Any]],
+                           model: Optional[str] = None,
+                           **params: Any) -> Iterator[Dict[str, Any]]:
+        """Yield every parsed SSE chunk of the stream as a dict: the role
+        chunk, one chunk per generated token (`delta.content`, and with
+        `logprobs=True` / `top_logprobs=n` a `logprobs.content` list of one
+        entry), then the finish_reason + usage chunk."""
+        body = {"model": self._model(model),
+                "messages": self._norm_messages(messages),
+                "stream": True, **params}
+        return self._chat_events(body)
+
+    def _chat_events(self, body: Dict[str, Any]) -> Iterator[Dict[str, Any]]:
         with self._req("POST", "/v1/chat/completions", body,
                        stream=True) as r:
-            for ev in parse_sse(iter(r)):
-                delta = ev.get("delta", {})
-                if delta.get("content"):
-                    yield delta["content"]
+            yield from parse_sse(iter(r))
 
     def embeddings(self, texts: List[str],
                    model: Optional[str] = None) -> Dict[str, Any]:

@@ -6,6 +6,8 @@ round-trips).  Speaks newline-delimited JSON over a Unix socket:
 
   -> {"type":"chat","id":r,"model":m,"messages":[...],"params":{...}}
   <- {"event":"delta","id":r,"text":t,"token_id":n}
+       + "logprob":{"token_id":n,"logprob":x,"top":[[id,lp],...]} when the
+         request's params ask: "logprobs": true, "top_logprobs": 0..20
   <- {"event":"done","id":r,"finish_reason":f,"usage":{...}}
   -> {"type":"abort","id":r}
   -> {"type":"info"}           <- {"event":"info","ready":true,...}
@@ -23,6 +25,14 @@ over it.  The stepping thread emits ONE batched line per engine step:
 
   <- {"event":"batch","items":[[rid,token_id], ...                  # delta
                                [rid,token_id,finish,in,out], ...]}  # final
+
+A step with rows that asked for logprobs adds a sibling key (absent
+otherwise, and `items` keeps its shape):
+
+     "lp":[[rid,lp_chosen,[id, ...],[lp, ...]], ...]
+
+--device-logprobs (EngineConfig.device_logprobs) keeps such rows in the
+pipelined decode; without it they take the synchronous step.
 
 Batch items carry bare token ids — the C++ gateway detokenizes
 (ByteDetok mirrors StreamDetokenizer), so the per-token Python cost is
@@ -332,7 +342,7 @@ class WorkerState:
                 fr = ((out.finish_reason.value if out.finish_reason
                        else "stop") if out.finished else None)
                 per_mux.setdefault(mux, []).append(
-                    (rid, out.token_id, fr))
+                    (rid, out.token_id, fr, out.logprobs))
                 if out.finished:
                     self.mux_of.pop(rid, None)
                 continue
@@ -469,8 +479,8 @@ class MuxChannel:
             self.meta_del.append(rid)
 
     def send_outputs(self, raw):
-        """Raw (rid, token_id, finish_reason|None) tuples from the GPU
-        loop; the writer thread does the rest."""
+        """Raw (rid, token_id, finish_reason|None, TokenLogprobs|None)
+        tuples from the GPU loop; the writer thread does the rest."""
         with self.cv:
             if self.dead:
                 return
@@ -491,8 +501,9 @@ class MuxChannel:
 
     def _encode(self, raw):
         items = []
+        lps = []
         meta = self.meta
-        for rid, tok, fr in raw:
+        for rid, tok, fr, lp in raw:
             m = meta.get(rid)
             if m is None:
                 continue               # aborted after the step ran
@@ -502,8 +513,13 @@ class MuxChannel:
             else:
                 items.append([rid, tok, fr, m[0], m[1]])
                 meta.pop(rid, None)
-        return (json.dumps({"event": "batch", "items": items},
-                           separators=(",", ":")) + "\n").encode()
+            if lp is not None:
+                lps.append([rid, _lp_json(lp.logprob),
+                            [t for t, _ in lp.top], [v for _, v in lp.top]])
+        line = {"event": "batch", "items": items}
+        if lps:
+            line["lp"] = lps
+        return (json.dumps(line, separators=(",", ":")) + "\n").encode()
 
     def _write_loop(self):
         while True:
@@ -540,8 +556,39 @@ class MuxChannel:
             self.cv.notify()
 
 
-def _mux_chat(msg, state: "WorkerState", mux: "MuxChannel", rids: set):
+def _sampling_params(msg, params, budget):
+    """SamplingParams of one chat message (both protocols).  `logprobs`
+    (bool) with `top_logprobs` (int, default 0) asks for per-token
+    log-probabilities; the engine refuses values outside 0..20."""
     from hyperspot.engine import SamplingParams
+    return SamplingParams(
+        temperature=float(params.get("temperature", 0.7)),
+        top_p=float(params.get("top_p", 1.0)),
+        top_k=int(params.get("top_k", 0)),
+        max_tokens=min(int(params.get("max_tokens", 256)), budget),
+        ignore_eos=bool(params.get("ignore_eos", False)),
+        seed=params.get("seed"),
+        response_format=params.get("response_format"),
+        response_schema=params.get("response_schema")
+        if isinstance(params.get("response_schema"), dict) else None,
+        tool_names=tuple(
+            (t.get("name") or t.get("function", {}).get("name"))
+            for t in (msg.get("tools") or [])
+            if isinstance(t, dict)
+            and (t.get("name") or t.get("function", {}).get("name"))),
+        logprobs=int(params.get("top_logprobs") or 0)
+        if params.get("logprobs") else None,
+    )
+
+
+_LP_FLOOR = -9999.0     # JSON has no -inf
+
+
+def _lp_json(v):
+    return v if v > _LP_FLOOR else _LP_FLOOR
+
+
+def _mux_chat(msg, state: "WorkerState", mux: "MuxChannel", rids: set):
     from .tokenizer import render_chat
 
     rid = msg.get("id") or f"r{time.monotonic_ns()}"
@@ -562,22 +609,12 @@ def _mux_chat(msg, state: "WorkerState", mux: "MuxChannel", rids: set):
                       "code": "validation_error",
                       "message": "prompt exceeds context window"})
         return
-    sampling = SamplingParams(
-        temperature=float(params.get("temperature", 0.7)),
-        top_p=float(params.get("top_p", 1.0)),
-        top_k=int(params.get("top_k", 0)),
-        max_tokens=min(int(params.get("max_tokens", 256)), budget),
-        ignore_eos=bool(params.get("ignore_eos", False)),
-        seed=params.get("seed"),
-        response_format=params.get("response_format"),
-        response_schema=params.get("response_schema")
-        if isinstance(params.get("response_schema"), dict) else None,
-        tool_names=tuple(
-            (t.get("name") or t.get("function", {}).get("name"))
-            for t in (msg.get("tools") or [])
-            if isinstance(t, dict)
-            and (t.get("name") or t.get("function", {}).get("name"))),
-    )
+    sampling = _sampling_params(msg, params, budget)
+    if sampling.logprobs is not None and not 0 <= sampling.logprobs <= 20:
+        mux.send_obj({"event": "error", "id": rid,
+                      "code": "validation_error",
+                      "message": "top_logprobs must be in 0..20"})
+        return
     rids.add(rid)
     state.submit_mux(rid, prompt_ids, sampling, mux)
 
@@ -734,7 +771,6 @@ def handle_conn(conn: socket.socket, state: WorkerState, model_name: str):
 
 
 def _run_chat(msg, state: WorkerState, send):
-    from hyperspot.engine import SamplingParams
     from .tokenizer import StreamDetokenizer, render_chat
 
     rid = msg.get("id") or f"r{time.monotonic_ns()}"
@@ -755,22 +791,11 @@ def _run_chat(msg, state: WorkerState, send):
               "code": "validation_error",
               "message": "prompt exceeds context window"})
         return
-    sampling = SamplingParams(
-        temperature=float(params.get("temperature", 0.7)),
-        top_p=float(params.get("top_p", 1.0)),
-        top_k=int(params.get("top_k", 0)),
-        max_tokens=min(int(params.get("max_tokens", 256)), budget),
-        ignore_eos=bool(params.get("ignore_eos", False)),
-        seed=params.get("seed"),
-        response_format=params.get("response_format"),
-        response_schema=params.get("response_schema")
-        if isinstance(params.get("response_schema"), dict) else None,
-        tool_names=tuple(
-            (t.get("name") or t.get("function", {}).get("name"))
-            for t in (msg.get("tools") or [])
-            if isinstance(t, dict)
-            and (t.get("name") or t.get("function", {}).get("name"))),
-    )
+    sampling = _sampling_params(msg, params, budget)
+    if sampling.logprobs is not None and not 0 <= sampling.logprobs <= 20:
+        send({"event": "error", "id": rid, "code": "validation_error",
+              "message": "top_logprobs must be in 0..20"})
+        return
     q = state.submit(rid, prompt_ids, sampling)
     detok = StreamDetokenizer(state.tokenizer)
     n_out = 0
@@ -788,19 +813,26 @@ def _run_chat(msg, state: WorkerState, send):
             return
         n_out += 1
         text = detok.push(out.token_id)
+        extra = {}
+        if out.logprobs is not None:
+            lp = out.logprobs
+            extra["logprob"] = {
+                "token_id": lp.token_id, "logprob": _lp_json(lp.logprob),
+                "top": [[t, v] for t, v in lp.top]}
         if not out.finished:
             # exactly ONE delta event per generated token (text may be ""
             # while a multi-byte UTF-8 sequence is incomplete) — REST
             # clients can count delivered tokens by counting deltas
             if not send({"event": "delta", "id": rid, "text": text,
-                         "token_id": out.token_id}):
+                         "token_id": out.token_id, **extra}):
                 state.abort(rid)
                 return
         if out.finished:
             text += detok.flush()
-            if text:
+            if text or extra:
+                # the last token's record travels even without text
                 send({"event": "delta", "id": rid, "text": text,
-                      "token_id": out.token_id})
+                      "token_id": out.token_id, **extra})
             send({"event": "done", "id": rid,
                   "finish_reason": out.finish_reason.value
                   if out.finish_reason else "stop",
@@ -860,6 +892,10 @@ def main():
                     help="sample top-k/top-p on the device at the decode "
                          "graph's tail, so stochastic rows stay in the "
                          "pipelined decode (EngineConfig.device_sampling)")
+    ap.add_argument("--device-logprobs", action="store_true",
+                    help="compute logprobs at the decode graph's tail, so "
+                         "rows that ask for them stay in the pipelined "
+                         "decode (EngineConfig.device_logprobs)")
     args = ap.parse_args()
 
     logging.basicConfig(level=logging.INFO,
@@ -880,7 +916,8 @@ def main():
         enforce_eager=args.eager or not on_gpu, tp_size=args.tp,
         quant=args.quant, kv_dtype=args.kv_dtype,
         prefill_paged_mfma=args.prefill_paged_mfma,
-        device_sampling=args.device_sampling)
+        device_sampling=args.device_sampling,
+        device_logprobs=args.device_logprobs)
     rank = 0
     # MoE models shard experts over the same ranks as TP attention
     # (config 4: Mixtral EP over RCCL all-to-all).  Decode graphs stay ON
