@@ -165,16 +165,35 @@ void paged_attn(torch::Tensor out, torch::Tensor q, torch::Tensor k_cache,
                     stream());
 }
 
+// What both MFMA prefill bindings ask of out, q, the kv head count,
+// seq_start and max_seqlen.
+void check_prefill_args(const torch::Tensor& out, const torch::Tensor& q,
+                        int KV, const torch::Tensor& seq_start,
+                        long max_seqlen) {
+  check(out, torch::kBFloat16, "out");
+  check_qkv_view(q, "q");
+  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(),
+              "out must be [T, H, D] like q");
+  const int H = (int)q.size(1);
+  TORCH_CHECK(KV > 0 && H % KV == 0, "GQA group: H=", H,
+              " is no multiple of KV=", KV);
+  check(seq_start, torch::kInt32, "seq_start");
+  TORCH_CHECK(seq_start.dim() == 1 && seq_start.numel() >= 1,
+              "seq_start must be [S+1]");
+  TORCH_CHECK(max_seqlen >= 0, "max_seqlen must be >= 0");
+}
+
 void attn_prefill_mfma(torch::Tensor out, torch::Tensor q, torch::Tensor k,
                        torch::Tensor v, torch::Tensor seq_start,
                        long max_seqlen, double scale) {
-  check(out, torch::kBFloat16, "out");
-  check_qkv_view(q, "q");
   check_qkv_view(k, "k");
   check_qkv_view(v, "v");
-  check(seq_start, torch::kInt32, "seq_start");
-  const int H = (int)q.size(1), D = (int)q.size(2);
   const int KV = (int)k.size(1);
+  check_prefill_args(out, q, KV, seq_start, max_seqlen);
+  const int H = (int)q.size(1), D = (int)q.size(2);
+  TORCH_CHECK(k.sizes() == v.sizes() && k.size(0) == q.size(0) &&
+                  k.size(2) == D,
+              "k/v must be [T, KV, D] with q's T and D, and equal-shaped");
   launch_attn_prefill_mfma(
       bf(out), cbf(q), cbf(k), cbf(v), seq_start.data_ptr<int>(),
       (int)seq_start.numel() - 1, (int)max_seqlen, H, KV, D, (float)scale,
@@ -191,18 +210,17 @@ void attn_prefill_paged_mfma(torch::Tensor out, torch::Tensor q,
                              torch::Tensor seq_start,
                              torch::Tensor ctx_start, long max_seqlen,
                              double scale) {
-  check(out, torch::kBFloat16, "out");
-  check_qkv_view(q, "q");
-  TORCH_CHECK(out.dim() == 3 && out.sizes() == q.sizes(),
-              "out must be [T, H, D] like q");
-  TORCH_CHECK(q.size(2) == 128,
-              "attn_prefill_paged_mfma: head_dim must be 128, got ",
-              q.size(2));
   TORCH_CHECK(k_cache.is_cuda() && v_cache.is_cuda() &&
                   k_cache.is_contiguous() && v_cache.is_contiguous(),
               "k_cache/v_cache must be contiguous GPU tensors");
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(),
               "k_cache/v_cache must be [NB, KV, 16, 128] and equal-shaped");
+  const int KV = (int)k_cache.size(1);
+  check_prefill_args(out, q, KV, seq_start, max_seqlen);
+  const int H = (int)q.size(1);
+  TORCH_CHECK(q.size(2) == 128,
+              "attn_prefill_paged_mfma: head_dim must be 128, got ",
+              q.size(2));
   TORCH_CHECK(k_cache.size(2) == 16,
               "attn_prefill_paged_mfma: page size must be 16, got ",
               k_cache.size(2));
@@ -213,20 +231,13 @@ void attn_prefill_paged_mfma(torch::Tensor out, torch::Tensor q,
   const bool kv_fp8 = k_cache.scalar_type() == torch::kFloat8_e4m3fn;
   TORCH_CHECK(kv_fp8 || k_cache.scalar_type() == torch::kBFloat16,
               "cache dtype must be bfloat16 or float8_e4m3fn");
-  const int H = (int)q.size(1), KV = (int)k_cache.size(1);
-  TORCH_CHECK(KV > 0 && H % KV == 0, "GQA group: H=", H,
-              " is no multiple of KV=", KV);
   check(block_tables, torch::kInt32, "block_tables");
-  check(seq_start, torch::kInt32, "seq_start");
   check(ctx_start, torch::kInt32, "ctx_start");
-  TORCH_CHECK(seq_start.dim() == 1 && seq_start.numel() >= 1,
-              "seq_start must be [S+1]");
   const int S = (int)seq_start.numel() - 1;
   TORCH_CHECK(ctx_start.dim() == 1 && ctx_start.numel() == S,
               "ctx_start must be [S] with S = seq_start.numel() - 1");
   TORCH_CHECK(block_tables.dim() == 2 && block_tables.size(0) == S,
               "block_tables must be [S, max_blocks]");
-  TORCH_CHECK(max_seqlen >= 0, "max_seqlen must be >= 0");
   launch_attn_prefill_paged_mfma(
       bf(out), cbf(q), cbf(k_cache), cbf(v_cache),
       block_tables.data_ptr<int>(), seq_start.data_ptr<int>(),

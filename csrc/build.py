@@ -48,7 +48,7 @@ def _includes():
 def _needs_build(src: Path, obj: Path) -> bool:
     if not obj.exists():
         return True
-    deps = [src, CSRC / "common.h", CSRC / "logit_scan.h", Path(__file__)]
+    deps = [src, *CSRC.glob("*.h"), Path(__file__)]
     return any(d.stat().st_mtime > obj.stat().st_mtime for d in deps)
 
 

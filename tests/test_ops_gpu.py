@@ -179,6 +179,64 @@ def test_attn_prefill_mfma_strided_views():
     assert torch.allclose(out.float().cpu(), ref, atol=2.5e-2, rtol=2.5e-2)
 
 
+def test_attn_prefill_mfma_empty_sequence_and_oversize_grid():
+    """An empty sequence between real ones, and max_seqlen 600 -> three q
+    tiles per (sequence, head) of which two own no row: the workgroups
+    without rows return early, every owned row is written."""
+    D, H, KV = 128, 8, 1
+    T = 49
+    q = _randn_bf16(T, H, D, seed=31)
+    k = _randn_bf16(T, KV, D, seed=32)
+    v = _randn_bf16(T, KV, D, seed=33)
+    ss = torch.tensor([0, 33, 33, 49], dtype=torch.int32, device=DEV)
+    out = torch.full_like(q, float("nan"))
+    from hyperspot import _C
+    _C.attn_prefill_mfma(out, q, k, v, ss, 600, D ** -0.5)
+    # the empty sequence owns no rows: the reference sees lens [33, 16]
+    ref = R.prefill_attn(q.float().cpu(), k.float().cpu(), v.float().cpu(),
+                         torch.tensor([0, 33, 49], dtype=torch.int32),
+                         D ** -0.5)
+    out = out.float().cpu()
+    assert torch.isfinite(out).all()
+    assert torch.allclose(out, ref, atol=2.5e-2, rtol=2.5e-2)
+
+
+def test_attn_prefill_mfma_rejects_bad_arguments():
+    from hyperspot import _C
+    T, H, KV, D = 17, 8, 1, 128
+    ss = torch.tensor([0, T], dtype=torch.int32, device=DEV)
+
+    def call(D=D, KV=KV, out_shape=None, ss=ss):
+        q = torch.zeros(T, H, D, dtype=torch.bfloat16, device=DEV)
+        k = torch.zeros(T, KV, D, dtype=torch.bfloat16, device=DEV)
+        out = torch.zeros(out_shape or q.shape, dtype=torch.bfloat16,
+                          device=DEV)
+        _C.attn_prefill_mfma(out, q, k, k.clone(), ss, T, D ** -0.5)
+
+    call()                                   # the base arguments are fine
+    with pytest.raises(RuntimeError, match="head_dim must be 128"):
+        call(D=64)
+    with pytest.raises(RuntimeError, match="like q"):
+        call(out_shape=(T, H * D))
+    with pytest.raises(RuntimeError, match="GQA group"):
+        call(KV=3)
+    with pytest.raises(RuntimeError, match="seq_start has wrong dtype"):
+        call(ss=ss.long())
+
+
+def test_attn_prefill_mfma_empty_step():
+    """No sequence and max_seqlen 0: returns without launching anything."""
+    from hyperspot import _C
+    D = 128
+    q = _randn_bf16(4, 8, D)
+    out = torch.full_like(q, float("nan"))
+    _C.attn_prefill_mfma(out, q, q[:, :2], q[:, :2],
+                         torch.zeros(1, dtype=torch.int32, device=DEV), 0,
+                         D ** -0.5)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+
+
 def test_silu_mul():
     x = _randn_bf16(65, 2 * 1024)
     out = ops.silu_mul(x)
