@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Isolated kernel microbenchmarks (GPU only) — us/call + achieved GB/s.
 
-Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|sample|logprobs|all]
+Usage: python bench_kernels.py [--which attn|gemm|fp8|prefill_paged|sample|logprobs|penalties|all]
                                [--iters N]
 
 Shapes mirror the flagship bench (Llama-3-8B bf16, bs=256 ctx=512 decode):
@@ -334,6 +334,95 @@ def bench_logprobs(iters, repeats=5):
         del logits
 
 
+def bench_penalties(iters, repeats=5):
+    """penalty_apply in place on [rows, 128256] bf16 logits: 256 penalty
+    rows with ~1k tokens of history each, alone and among 2048 rows, and
+    launches in which no row has a slot (what device_penalties adds to a
+    decode graph without penalty rows), with penalty_note beside them.
+    The floor counts what a penalty row must move, 2 bytes of logit and 4
+    of state per token read plus 2 per seen token written, at the 6.29
+    TB/s measured for a float4 copy on this GPU.  Each call penalises the
+    logits the last one left, so seen logits end at -inf and are no longer
+    written; the written share is under 1 % of the floor either way."""
+    import hyperspot.ops as ops
+    dev = "cuda:0"
+    vocab, nslots, hist_len = 128256, 256, 1024
+    g = torch.Generator().manual_seed(3)
+    table = torch.zeros(nslots, vocab, dtype=torch.int32, device=dev)
+    toks = torch.randint(0, vocab, (nslots * hist_len,), generator=g,
+                         dtype=torch.int32).to(dev)
+    off = (torch.arange(nslots + 1, dtype=torch.int32) * hist_len).to(dev)
+    plen = torch.full((nslots,), hist_len // 2, dtype=torch.int32, device=dev)
+    ops.penalty_build(table, torch.arange(nslots, dtype=torch.int32,
+                                          device=dev), toks, off, plen)
+    seen = int((table != 0).sum())
+    for rows in (256, 2048):
+        logits = torch.empty(rows, vocab, dtype=torch.bfloat16, device=dev)
+        for r0 in range(0, rows, 256):
+            n = min(256, rows - r0)
+            logits[r0:r0 + n] = (torch.randn(n, vocab, generator=g) * 3).to(
+                torch.bfloat16).to(dev)
+        sampled = torch.randint(0, vocab, (rows,), generator=g).to(dev)
+        rep = torch.full((rows,), 1.1, device=dev)
+        pres = torch.full((rows,), 0.5, device=dev)
+        freq = torch.full((rows,), 0.25, device=dev)
+        none = torch.full((rows,), -1, dtype=torch.int32, device=dev)
+        slot = none.clone()
+        # the penalty rows spread over the batch, slots in shuffled order
+        where = torch.arange(nslots) * (rows // nslots)
+        slot[where] = torch.randperm(nslots, generator=g).to(
+            torch.int32).to(dev)
+        floor_us = (nslots * vocab * 6 + seen * 2) / 6.29e6
+        cases = [
+            ("penalty_apply", "no row", lambda: ops.penalty_apply(
+                logits, none, rep, pres, freq, table)),
+            ("penalty_apply", "256 rows", lambda: ops.penalty_apply(
+                logits, slot, rep, pres, freq, table)),
+            ("penalty_note", "no row", lambda: ops.penalty_note(
+                table, none, sampled)),
+            ("penalty_note", "256 rows", lambda: ops.penalty_note(
+                table, slot, sampled)),
+        ]
+        times = {i: [] for i in range(len(cases))}
+        for r in range(repeats):
+            for i, (_, _, fn) in enumerate(cases):
+                times[i].append(timed(fn, iters, warmup=20 if r == 0 else 3))
+        for i, (name, what, _) in enumerate(cases):
+            t = sorted(times[i])
+            us = t[repeats // 2]
+            rec = {"kernel": name, "shape": f"{rows}x{vocab}",
+                   "penalty_rows": what, "us": round(us, 1),
+                   "us_min": round(t[0], 1), "us_max": round(t[-1], 1)}
+            if i == 1:
+                # the 197 MB a call touches fit the 256 MB Infinity Cache,
+                # and back-to-back calls find them there; in a decode step
+                # 16 GB of weights have streamed past since the last call.
+                # So also time single calls behind a 1 GiB fill.
+                flush = torch.empty(1 << 28, dtype=torch.int32, device=dev)
+                cold = []
+                for k in range(21):
+                    flush.fill_(k)
+                    s = torch.cuda.Event(enable_timing=True)
+                    e = torch.cuda.Event(enable_timing=True)
+                    s.record()
+                    cases[1][2]()
+                    e.record()
+                    torch.cuda.synchronize()
+                    cold.append(s.elapsed_time(e) * 1e3)
+                del flush
+                cold = sorted(cold[1:])
+                rec.update(floor_us=round(floor_us, 1),
+                           x_floor=round(us / floor_us, 2),
+                           cold_us=round(cold[len(cold) // 2], 1),
+                           cold_us_min=round(cold[0], 1),
+                           cold_us_max=round(cold[-1], 1),
+                           x_floor_cold=round(
+                               cold[len(cold) // 2] / floor_us, 2),
+                           seen_tokens=seen)
+            print(json.dumps(rec), flush=True)
+        del logits
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--which", default="attn")
@@ -352,6 +441,8 @@ def main():
         bench_sample(args.iters)
     if args.which in ("logprobs", "all"):
         bench_logprobs(args.iters)
+    if args.which in ("penalties", "all"):
+        bench_penalties(args.iters)
 
 
 if __name__ == "__main__":

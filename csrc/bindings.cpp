@@ -56,6 +56,13 @@ void launch_token_logprobs(float*, int*, const bf16*, const long*, const int*,
                            long, int, hipStream_t);
 void launch_decode_advance(long*, long*, int*, long*, int*, const long*,
                            const int*, int, int, int, hipStream_t);
+void launch_penalty_build(int*, const int*, const int*, const int*,
+                          const int*, int, int, int, int, hipStream_t);
+void launch_penalty_apply(bf16*, const int*, const float*, const float*,
+                          const float*, const int*, long, int, int,
+                          hipStream_t);
+void launch_penalty_note(int*, const int*, const long*, long, int, int,
+                         hipStream_t);
 
 namespace {
 
@@ -356,6 +363,86 @@ void decode_advance(torch::Tensor input_ids, torch::Tensor positions,
                         stream());
 }
 
+// Penalty state (csrc/penalties.hip): table int32 [slots, vocab], word =
+// 2 * count among generated tokens + (token occurs in the prompt).
+void check_penalty_table(const torch::Tensor& table) {
+  check(table, torch::kInt32, "table");
+  TORCH_CHECK(table.dim() == 2 && table.size(0) > 0 && table.size(1) > 0,
+              "table must be int32 [slots, vocab]");
+  TORCH_CHECK(table.size(0) < (1LL << 30) && table.size(1) < (1LL << 30),
+              "table too large");
+}
+
+// Row slots[i] of the table := history tokens[offsets[i]:offsets[i+1]], the
+// first prompt_len[i] of them prompt.  Not for capture (the grid is n).
+void penalty_build(torch::Tensor table, torch::Tensor slots,
+                   torch::Tensor tokens, torch::Tensor offsets,
+                   torch::Tensor prompt_len) {
+  check_penalty_table(table);
+  check(slots, torch::kInt32, "slots");
+  check(tokens, torch::kInt32, "tokens");
+  check(offsets, torch::kInt32, "offsets");
+  check(prompt_len, torch::kInt32, "prompt_len");
+  const int64_t n = slots.numel();
+  TORCH_CHECK(offsets.numel() == n + 1 && prompt_len.numel() == n,
+              "penalty_build: offsets must hold n + 1, prompt_len n entries");
+  TORCH_CHECK(tokens.numel() < (1LL << 31), "too many history tokens");
+  for (const torch::Tensor* t : {&slots, &tokens, &offsets, &prompt_len})
+    TORCH_CHECK(t->device() == table.device(),
+                "penalty_build: tensors on different devices");
+  launch_penalty_build(table.data_ptr<int>(), slots.data_ptr<int>(),
+                       tokens.data_ptr<int>(), offsets.data_ptr<int>(),
+                       prompt_len.data_ptr<int>(), (int)n,
+                       (int)table.size(0), (int)table.size(1),
+                       (int)tokens.numel(), stream());
+}
+
+// In place on logits [rows, vocab]; rows with slot < 0 are left alone.
+void penalty_apply(torch::Tensor logits, torch::Tensor slot,
+                   torch::Tensor rep, torch::Tensor pres, torch::Tensor freq,
+                   torch::Tensor table) {
+  check_penalty_table(table);
+  check(logits, torch::kBFloat16, "logits");
+  check(slot, torch::kInt32, "slot");
+  check(rep, torch::kFloat32, "rep");
+  check(pres, torch::kFloat32, "pres");
+  check(freq, torch::kFloat32, "freq");
+  TORCH_CHECK(logits.dim() == 2 && logits.size(1) == table.size(1),
+              "logits must be [rows, vocab] with the table's vocab");
+  const int64_t rows = logits.size(0);
+  // the grid is rows * chunks of 8192 logits
+  TORCH_CHECK(rows * (table.size(1) / 8192 + 2) < (1LL << 31),
+              "rows * vocab too large");
+  TORCH_CHECK(slot.numel() >= rows && rep.numel() >= rows &&
+                  pres.numel() >= rows && freq.numel() >= rows,
+              "per-row tensors must have at least `rows` elements");
+  for (const torch::Tensor* t : {&slot, &rep, &pres, &freq, &table})
+    TORCH_CHECK(t->device() == logits.device(),
+                "penalty_apply: tensors on different devices");
+  launch_penalty_apply(bf(logits), slot.data_ptr<int>(),
+                       rep.data_ptr<float>(), pres.data_ptr<float>(),
+                       freq.data_ptr<float>(), table.data_ptr<int>(), rows,
+                       (int)table.size(0), (int)table.size(1), stream());
+}
+
+// table[slot[r], sampled[r]] += 2 for the first `rows` = sampled.numel()
+// rows with slot >= 0 and a token inside the vocabulary.
+void penalty_note(torch::Tensor table, torch::Tensor slot,
+                  torch::Tensor sampled) {
+  check_penalty_table(table);
+  check(slot, torch::kInt32, "slot");
+  check(sampled, torch::kInt64, "sampled");
+  const int64_t rows = sampled.numel();
+  TORCH_CHECK(slot.numel() >= rows,
+              "slot must have at least `rows` elements");
+  TORCH_CHECK(slot.device() == table.device() &&
+                  sampled.device() == table.device(),
+              "penalty_note: tensors on different devices");
+  launch_penalty_note(table.data_ptr<int>(), slot.data_ptr<int>(),
+                      sampled.data_ptr<long>(), rows, (int)table.size(0),
+                      (int)table.size(1), stream());
+}
+
 }  // namespace
 
 
@@ -501,4 +588,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sample_fused", &sample_fused);
   m.def("token_logprobs", &token_logprobs);
   m.def("decode_advance", &decode_advance);
+  m.def("penalty_build", &penalty_build);
+  m.def("penalty_apply", &penalty_apply);
+  m.def("penalty_note", &penalty_note);
 }

@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <cstring>
 #include <unordered_map>
 
@@ -635,6 +636,8 @@ void LlmGatewayModule::spawn_one(Worker& wk) {
         args.push_back("--device-sampling");
       if (worker_cfg_.at("device_logprobs").as_bool(false))
         args.push_back("--device-logprobs");
+      if (worker_cfg_.at("device_penalties").as_bool(false))
+        args.push_back("--device-penalties");
     }
     std::vector<char*> argv;
     for (auto& a : args) argv.push_back(const_cast<char*>(a.c_str()));
@@ -814,6 +817,36 @@ static void validate_logprobs(const Json& body) {
                   "validation_error"};
 }
 
+// ---- penalties (OpenAI-style `presence_penalty` / `frequency_penalty`,
+// and `repetition_penalty`) ----
+
+// 400 unless each field that is given is a number: the first two in
+// [-2, 2], the third > 0 (the engine's SamplingParams.check_penalties)
+static void validate_penalties(const Json& body) {
+  for (const char* f : {"presence_penalty", "frequency_penalty",
+                        "repetition_penalty"}) {
+    const Json& v = body.at(f);
+    if (v.is_null()) continue;
+    const bool rep = f[0] == 'r';
+    const double x = v.as_number(0);
+    const bool ok = v.is_number() && std::isfinite(x) &&
+                    (rep ? x > 0 : (x >= -2 && x <= 2));
+    if (!ok)
+      throw Problem{400, "Bad Request", "about:blank",
+                    std::string("'") + f +
+                        (rep ? "' must be a number > 0"
+                             : "' must be a number in [-2, 2]"),
+                    "validation_error"};
+  }
+}
+
+// forward the fields that are given to the worker
+static void forward_penalties(const Json& body, Json& params) {
+  for (const char* f : {"presence_penalty", "frequency_penalty",
+                        "repetition_penalty"})
+    if (body.contains(f) && !body.at(f).is_null()) params[f] = body.at(f);
+}
+
 // forward both fields to the worker; true when the request asks
 static bool forward_logprobs(const Json& body, Json& params) {
   for (const char* f : {"logprobs", "top_logprobs"})
@@ -870,6 +903,7 @@ Json LlmGatewayModule::run_chat_blocking(const Json& body,
   for (const char* f : {"temperature", "top_p", "top_k", "max_tokens",
                         "seed", "ignore_eos", "response_format"})
     if (body.contains(f)) params[f] = body.at(f);
+  forward_penalties(body, params);
   const bool want_lp = forward_logprobs(body, params);
   // reference request schema: `response_schema` asks for structured
   // output — the engine enforces the JSON grammar via constrained
@@ -1106,6 +1140,7 @@ void LlmGatewayModule::chat_handler(HttpRequest& req, ResponseWriter& w) {
                   "validation_error"};
   const bool stream = body.at("stream").as_bool(false);
   validate_logprobs(body);
+  validate_penalties(body);
 
   SecurityContext sec =
       SecurityContext::from_json(req.extensions.at("security"));
@@ -1214,6 +1249,7 @@ void LlmGatewayModule::chat_handler(HttpRequest& req, ResponseWriter& w) {
   for (const char* f : {"temperature", "top_p", "top_k", "max_tokens",
                         "seed", "ignore_eos", "response_format"})
     if (body.contains(f)) params[f] = body.at(f);
+  forward_penalties(body, params);
   const bool want_lp = forward_logprobs(body, params);
   // reference request schema: `response_schema` asks for structured
   // output — the engine enforces the JSON grammar via constrained
@@ -1669,6 +1705,16 @@ void LlmGatewayModule::register_rest(ModuleCtx& ctx, RestRegistry& rest) {
     tl["minimum"] = (long)0;
     tl["maximum"] = (long)20;
     props["top_logprobs"] = tl;
+    Json pen = Json::object();
+    pen["type"] = "number";
+    pen["minimum"] = -2.0;
+    pen["maximum"] = 2.0;
+    props["presence_penalty"] = pen;
+    props["frequency_penalty"] = pen;
+    Json rp = Json::object();
+    rp["type"] = "number";
+    rp["exclusiveMinimum"] = 0.0;
+    props["repetition_penalty"] = rp;
     req_schema["properties"] = props;
     Json required = Json::array();
     required.push_back("model");

@@ -142,6 +142,15 @@ class EngineConfig:
     # default, so that the default graphs launch what they always did;
     # logprob rows then take the synchronous step
     device_logprobs: bool = False
+    # keep rows with presence / frequency / repetition penalties in the
+    # pipelined decode: every decode graph then runs ops.penalty_apply in
+    # front of the sampler and ops.penalty_note behind it, on a count table
+    # int32 [max_penalty_seqs, vocab] allocated with the engine (131 MB at
+    # Llama's vocabulary and 256 slots).  Off by default, so that the
+    # default graphs launch what they always did; penalty rows then take
+    # the synchronous step, and the table is allocated at the first one
+    device_penalties: bool = False
+    max_penalty_seqs: int = 256          # slots of the penalty count table
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,
@@ -187,9 +196,46 @@ class SamplingParams:
     # per-token log-probabilities: None = off, 0 = the sampled token only,
     # 1..20 = plus that many most likely alternatives.  The distribution
     # is the one the token was chosen from at temperature 1, before top-k
-    # and top-p (after the guided-decoding mask)
+    # and top-p (after the penalties below and the guided-decoding mask):
+    # a record describes the penalised logits the token was chosen from
     logprobs: Optional[int] = None
+    # OpenAI-style penalties on the tokens the request has seen, applied
+    # to the logits before anything else (guided mask, sampler, logprobs).
+    # repetition_penalty r divides the positive and multiplies the other
+    # logits of every token of prompt or output; frequency_penalty times
+    # a token's count among the GENERATED tokens, and presence_penalty
+    # once if that count is not zero, are subtracted.  presence and
+    # frequency lie in [-2, 2], r > 0; (0, 0, 1) = no penalty
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
 
     @property
     def greedy(self) -> bool:
         return self.temperature == 0.0
+
+    @property
+    def penalized(self) -> bool:
+        return not (self.presence_penalty == 0 and self.frequency_penalty == 0
+                    and self.repetition_penalty == 1)
+
+    def check_penalties(self) -> None:
+        """ValueError unless the three penalties are finite and in range."""
+        import math
+        for name, lo, hi in (("presence_penalty", -2.0, 2.0),
+                             ("frequency_penalty", -2.0, 2.0),
+                             ("repetition_penalty", 0.0, math.inf)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, (int, float)) \
+                    or not math.isfinite(v):
+                raise ValueError(
+                    f"SamplingParams.{name} must be a finite number, "
+                    f"got {v!r}")
+            if name == "repetition_penalty":
+                if v <= 0:
+                    raise ValueError(
+                        f"SamplingParams.repetition_penalty must be > 0, "
+                        f"got {v!r}")
+            elif not lo <= v <= hi:
+                raise ValueError(
+                    f"SamplingParams.{name} must lie in [-2, 2], got {v!r}")

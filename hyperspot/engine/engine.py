@@ -44,6 +44,8 @@ class LLMEngine:
         if lp is not None and not (isinstance(lp, int) and 0 <= lp <= 20):
             raise ValueError(
                 f"SamplingParams.logprobs must be None or 0..20, got {lp!r}")
+        if sampling is not None:
+            sampling.check_penalties()
         req = Request(request_id=rid,
                       prompt_token_ids=list(prompt_token_ids),
                       sampling=sampling or SamplingParams(),
@@ -105,12 +107,17 @@ class LLMEngine:
 
     def _pipe_eligible(self) -> bool:
         """Every running row unguided, greedy unless the device samples
-        (EngineConfig.device_sampling), and without logprobs unless the
-        decode graphs compute them (EngineConfig.device_logprobs): the
-        next decode step's inputs then depend on the in-flight tokens only
-        through input_ids, which the device already holds."""
+        (EngineConfig.device_sampling), without logprobs unless the
+        decode graphs compute them (EngineConfig.device_logprobs), and
+        without penalties unless the graphs apply them and keep the counts
+        (EngineConfig.device_penalties; at most max_penalty_seqs such
+        rows): the next decode step's inputs then depend on the in-flight
+        tokens only through input_ids and those counts, which the device
+        already holds."""
         stochastic_ok = self.config.device_sampling
         logprobs_ok = self.config.device_logprobs
+        penalties_ok = self.config.device_penalties
+        npen = 0
         for r in self.scheduler.running:
             sp = r.sampling
             if (sp.temperature != 0 and not stochastic_ok) \
@@ -118,6 +125,10 @@ class LLMEngine:
                     or sp.response_schema is not None \
                     or sp.response_format in ("json", "tool_call"):
                 return False
+            if sp.penalized:
+                npen += 1
+                if not penalties_ok or npen > self.config.max_penalty_seqs:
+                    return False
         return True
 
     def step_pipelined(self) -> List[StepOutput]:

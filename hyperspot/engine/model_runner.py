@@ -180,6 +180,13 @@ class ModelRunner:
                                              pin_memory=pin)
                 slot["lp_id"] = torch.empty(cap, cols, dtype=torch.int32,
                                             pin_memory=pin)
+        # penalty count table int32 [max_penalty_seqs, vocab] (csrc/
+        # penalties.hip).  With device_penalties it is part of the decode
+        # graphs and allocated here, behind the KV pool; without, the first
+        # step that has a penalty row allocates it
+        self._pen_table: Optional[torch.Tensor] = None
+        if config.device_penalties:
+            self._penalty_table()
         # logprob records of the last execute(), one per batch row (None =
         # the row did not ask), or None when no row asked
         self.last_logprobs: Optional[List[Optional[TokenLogprobs]]] = None
@@ -375,6 +382,8 @@ class ModelRunner:
                 io["temperature"].zero_()     # the tail is a plain argmax
             if self.config.device_logprobs:
                 io["lp_n"].fill_(-1)          # and computes no logprobs
+            if self.config.device_penalties:
+                io["pen_slot"].fill_(-1)      # and penalises no row
             io["passthrough"] = True
         io["input_ids"][:B] = input_ids
         io["input_ids"][B:] = 0
@@ -483,6 +492,14 @@ class ModelRunner:
                                       dtype=torch.float32, device=d)
             io["lp_id"] = torch.full((rows, cols), -1, dtype=torch.int32,
                                      device=d)
+        if self.config.device_penalties:
+            # pen_slot -1 = not a penalty row: padding rows, pass-through
+            # replays, rows whose three penalties are neutral
+            io["pen_slot"] = torch.full((rows,), -1, dtype=torch.int32,
+                                        device=d)
+            io["pen_rep"] = torch.ones(rows, dtype=torch.float32, device=d)
+            io["pen_pres"] = torch.zeros(rows, dtype=torch.float32, device=d)
+            io["pen_freq"] = torch.zeros(rows, dtype=torch.float32, device=d)
         if not self.config.device_sampling:
             io["ctl"] = torch.full((4 * rows + 4,), -1, dtype=torch.int32,
                                    device=d)
@@ -500,11 +517,25 @@ class ModelRunner:
         return io
 
     def _pipe_tail(self, io: dict, logits: torch.Tensor) -> None:
+        pen = self.config.device_penalties
+        if pen:
+            # first, so that the sampler and the logprobs see the
+            # penalised logits
+            ops.penalty_apply(logits, io["pen_slot"], io["pen_rep"],
+                              io["pen_pres"], io["pen_freq"],
+                              self._pen_table)
         if self.config.device_sampling:
             ops.sample_fused(logits, io["temperature"], io["top_p"],
                              io["top_k"], io["uniform"], out=io["sampled"])
         else:
             ops.greedy_sample(logits, out=io["sampled"])
+        if pen:
+            # the next step's penalty_apply counts this token.  A row that
+            # runs a step past its end (EOS seen one step late, dropped,
+            # aborted) or idles as a padding row in place still notes a
+            # token into its own slot: nothing reads that slot again before
+            # the next re-seed rebuilds it
+            ops.penalty_note(self._pen_table, io["pen_slot"], io["sampled"])
         if self.config.device_logprobs:
             ops.token_logprobs(logits, io["sampled"], io["lp_n"],
                                io["lp_val"], io["lp_id"])
@@ -594,6 +625,24 @@ class ModelRunner:
                  for r in reqs], dtype=torch.int32)
             io["lp_n"].copy_(lp)
             self._pipe["lp_n"] = lp[:B].numpy()
+        if self.config.device_penalties:
+            self._pipe_seed_penalties(reqs, io, nrows)
+
+    def _pipe_seed_penalties(self, reqs: List[Request], io: dict,
+                             nrows: int) -> None:
+        """Give each penalty row a table slot, build the slots from the
+        histories and upload the four per-row vectors (once per re-seed).
+        Nothing is in flight at a re-seed, so the host knows every history
+        completely, the last token included: that one goes into this step
+        through decode_advance's host-id path and is in the built counts
+        already, so penalty_note only ever counts newly sampled tokens.
+        _pipe_eligible has seen to it that the slots suffice."""
+        rows = [i for i, r in enumerate(reqs) if r.sampling.penalized]
+        slot, par = self._penalty_rows(reqs, rows, nrows)
+        io["pen_slot"].copy_(slot)
+        io["pen_rep"].copy_(par[0])
+        io["pen_pres"].copy_(par[1])
+        io["pen_freq"].copy_(par[2])
 
     def _pipe_seed_sampling(self, reqs: List[Request], io: dict,
                             nrows: int) -> None:
@@ -837,11 +886,91 @@ class ModelRunner:
         logits[gidx, NB:] = neg
         logits[gidx, :NB] += small.to(device=d, dtype=logits.dtype)
 
+    # ---------------- penalties ----------------
+
+    def _penalty_table(self) -> torch.Tensor:
+        if self._pen_table is None:
+            self._pen_table = torch.zeros(
+                max(self.config.max_penalty_seqs, 1), self.spec.vocab_size,
+                dtype=torch.int32, device=self.device)
+        return self._pen_table
+
+    def _penalty_build(self, reqs: List[Request]) -> None:
+        """Table slots 0..len(reqs)-1 := the requests' histories, uploaded
+        as one flat int32 tensor.  The generated tokens are the last
+        num_generated of prompt + output, not output_token_ids: preemption
+        folds the outputs into the prompt, and num_generated survives."""
+        import numpy as np
+        n = len(reqs)
+        off = np.zeros(n + 1, dtype=np.int32)
+        plen = np.empty(n, dtype=np.int32)
+        hist: List[int] = []
+        for i, r in enumerate(reqs):
+            hist.extend(r.prompt_token_ids)
+            hist.extend(r.output_token_ids)
+            off[i + 1] = len(hist)
+            plen[i] = r.num_tokens - r.num_generated
+        d = self.device
+        # ids that do not fit int32 lie outside any vocabulary: -1 skips
+        toks = np.asarray(hist, dtype=np.int64)
+        toks[(toks < 0) | (toks > 0x7fffffff)] = -1
+        ops.penalty_build(
+            self._penalty_table(),
+            torch.arange(n, dtype=torch.int32).to(d),
+            torch.from_numpy(toks.astype(np.int32)).to(d),
+            torch.from_numpy(off).to(d), torch.from_numpy(plen).to(d))
+
+    def _penalty_rows(self, requests: List[Request], rows: List[int],
+                      nrows: int):
+        """Rows `rows` of the batch take table slots 0..len(rows)-1, built
+        from their histories.  Returns the per-row vectors of an
+        `nrows`-row launch on the host: slot int32 (-1 elsewhere) and
+        float32 [3, nrows] = repetition (1 elsewhere) | presence |
+        frequency (0 elsewhere)."""
+        par = torch.zeros(3, nrows, dtype=torch.float32)
+        par[0].fill_(1.0)
+        slot = torch.full((nrows,), -1, dtype=torch.int32)
+        for k, i in enumerate(rows):
+            sp = requests[i].sampling
+            slot[i] = k
+            par[0, i] = sp.repetition_penalty
+            par[1, i] = sp.presence_penalty
+            par[2, i] = sp.frequency_penalty
+        if rows:
+            self._penalty_build([requests[i] for i in rows])
+        return slot, par
+
+    def _apply_penalties(self, logits: torch.Tensor,
+                         requests: List[Request]) -> None:
+        """Penalties of the synchronous step, in place on its logits and
+        before anything else reads them.  The penalty rows that sample a
+        token this step (not a mid-prompt chunk) take scratch slots
+        0..k-1 of the table, max_penalty_seqs at a time, rebuilt from the
+        host's histories every step; the pipelined state that may live in
+        those slots is invalid after a synchronous step anyway.  On a
+        request's first prefill every token is prompt, so only
+        repetition_penalty acts; a prefill that recomputes a preempted
+        request still counts the outputs folded into its prompt as
+        generated.  No penalty row: no op is called, no table allocated."""
+        rows = [i for i, r in enumerate(requests) if r.sampling.penalized
+                and r.num_computed_tokens >= r.num_prompt_tokens]
+        if not rows:
+            return
+        S = self._penalty_table().shape[0]
+        R = logits.shape[0]
+        d = logits.device
+        for k0 in range(0, len(rows), S):
+            slot, par = self._penalty_rows(requests, rows[k0:k0 + S], R)
+            par = par.to(d)
+            ops.penalty_apply(logits, slot.to(d), par[0], par[1], par[2],
+                              self._pen_table)
+
     def _sample(self, logits: torch.Tensor, requests: List[Request]) -> torch.Tensor:
+        self._apply_penalties(logits, requests)
         self._apply_guided(logits, requests)
         tokens = self._sample_tokens(logits, requests)
-        # after the token is chosen, on the (guided-masked) logits it was
-        # chosen from; the records wait in last_logprobs for LLMEngine.step
+        # after the token is chosen, on the (penalised, guided-masked) logits
+        # it was chosen from; the records wait in last_logprobs for LLMEngine.step
         n_top = [-1 if r.sampling.logprobs is None else r.sampling.logprobs
                  for r in requests]
         self.last_logprobs = None

@@ -424,6 +424,53 @@ def token_logprobs(logits: torch.Tensor, chosen: torch.Tensor,
     return torch_ref.token_logprobs(logits, chosen, n_top, out_val, out_id)
 
 
+def penalty_build(table: torch.Tensor, slots: torch.Tensor,
+                  tokens: torch.Tensor, offsets: torch.Tensor,
+                  prompt_len: torch.Tensor) -> None:
+    """Make rows of the penalty table encode whole histories
+    (csrc/penalties.hip).
+
+    table int32 [slots, vocab]; slots int32 [n] (distinct); tokens int32
+    [total], the histories back to back; offsets int32 [n + 1]; prompt_len
+    int32 [n]: how many of history i's first tokens are prompt.  A word is
+    2 * (count among the generated tokens) + (occurs in the prompt); ids
+    outside the vocabulary are skipped, and the row's earlier content is
+    gone.  The grid depends on n: not for capture."""
+    if table.is_cuda:
+        _native().penalty_build(table, slots, tokens, offsets, prompt_len)
+        return
+    torch_ref.penalty_build(table, slots, tokens, offsets, prompt_len)
+
+
+def penalty_apply(logits: torch.Tensor, slot: torch.Tensor,
+                  rep: torch.Tensor, pres: torch.Tensor, freq: torch.Tensor,
+                  table: torch.Tensor) -> None:
+    """Repetition / frequency / presence penalties in place on logits
+    [rows, vocab], from the counts in `table` (csrc/penalties.hip).
+
+    slot int32, rep / pres / freq float32, each at least [rows] and read on
+    the device, so the launch depends on rows and vocab alone and can be
+    captured.  slot[r] < 0 = not a penalty row, left untouched, as is every
+    logit whose token the row has not seen.  torch_ref.penalty_apply spells
+    the arithmetic out; the kernel matches it bit for bit.  bf16 GPU logits
+    go to the kernel, anything else to the torch twin."""
+    if logits.is_cuda and logits.dtype == torch.bfloat16:
+        _native().penalty_apply(logits, slot, rep, pres, freq, table)
+        return
+    torch_ref.penalty_apply(logits, slot, rep, pres, freq, table)
+
+
+def penalty_note(table: torch.Tensor, slot: torch.Tensor,
+                 sampled: torch.Tensor) -> None:
+    """Count the token each penalty row has just sampled: table[slot[r],
+    sampled[r]] += 2 for r < len(sampled) with slot[r] >= 0 and the token
+    inside the vocabulary.  sampled int64 [rows]; capturable."""
+    if table.is_cuda:
+        _native().penalty_note(table, slot, sampled)
+        return
+    torch_ref.penalty_note(table, slot, sampled)
+
+
 def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
                    seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
                    block_tables: torch.Tensor, sampled_prev: torch.Tensor,

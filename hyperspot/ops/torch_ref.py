@@ -352,6 +352,73 @@ def token_logprobs(logits: torch.Tensor, chosen: torch.Tensor,
     return out_val, out_id
 
 
+def penalty_build(table: torch.Tensor, slots: torch.Tensor,
+                  tokens: torch.Tensor, offsets: torch.Tensor,
+                  prompt_len: torch.Tensor) -> None:
+    """Twin of csrc/penalties.hip penalty_build.  table int32 [slots, V];
+    row slots[i] := history tokens[offsets[i]:offsets[i+1]], the first
+    prompt_len[i] of them prompt: word = 2 * count among the generated
+    tokens + (token occurs in the prompt).  Ids outside [0, V) are skipped;
+    whatever the row held before is gone."""
+    S, V = table.shape
+    off = offsets.tolist()
+    for i, slot in enumerate(slots.tolist()):
+        if slot < 0 or slot >= S:
+            continue
+        h = tokens[max(off[i], 0):off[i + 1]].long()
+        n = int(prompt_len[i])
+        ok = (h >= 0) & (h < V)
+        pos = torch.arange(h.numel(), device=h.device)
+        gen = torch.bincount(h[ok & (pos >= n)], minlength=V)
+        pro = torch.bincount(h[ok & (pos < n)], minlength=V) > 0
+        table[slot] = (2 * gen + pro.long()).to(torch.int32)
+
+
+def penalty_apply(logits: torch.Tensor, slot: torch.Tensor,
+                  rep: torch.Tensor, pres: torch.Tensor, freq: torch.Tensor,
+                  table: torch.Tensor) -> None:
+    """Twin of penalty_apply, in place on logits [R, V].  For rows with
+    slot >= 0 and tokens whose table word is non-zero, in float32 and one
+    rounded operation at a time (the kernel is held to the same bits):
+        q = l / r if l > 0 else l * r
+        q = q - f * c            c = word >> 1
+        q = q - (p if c > 0 else 0)
+    rounded to the logits' dtype.  Other logits, and NaN, keep their bits."""
+    R = logits.shape[0]
+    S = table.shape[0]
+    sl = slot[:R].long()
+    rows = torch.nonzero((sl >= 0) & (sl < S)).flatten()
+    if rows.numel() == 0:
+        return
+    w = table[sl[rows]]
+    c = w >> 1
+    old = logits[rows]
+    l = old.to(torch.float32)
+    r = rep[:R][rows].to(torch.float32)[:, None]
+    p = pres[:R][rows].to(torch.float32)[:, None]
+    f = freq[:R][rows].to(torch.float32)[:, None]
+    q = torch.where(l > 0, l / r, l * r)
+    fc = f * c.to(torch.float32)
+    q = q - fc
+    q = q - torch.where(c > 0, p, torch.zeros_like(p))
+    new = q.to(logits.dtype)
+    logits[rows] = torch.where((w != 0) & ~torch.isnan(l), new, old)
+
+
+def penalty_note(table: torch.Tensor, slot: torch.Tensor,
+                 sampled: torch.Tensor) -> None:
+    """Twin of penalty_note: table[slot[r], sampled[r]] += 2 for the rows
+    r < len(sampled) with a slot and a token inside the vocabulary."""
+    S, V = table.shape
+    R = sampled.numel()
+    sl = slot[:R].long()
+    t = sampled.long()
+    ok = (sl >= 0) & (sl < S) & (t >= 0) & (t < V)
+    table.index_put_((sl[ok], t[ok]),
+                     torch.full((int(ok.sum()),), 2, dtype=table.dtype,
+                                device=table.device), accumulate=True)
+
+
 def moe_route(hidden: torch.Tensor, router_w: torch.Tensor, top_k: int):
     """Softmax-topk routing: returns (weights [T,K], expert_ids [T,K])."""
     logits = hidden.float() @ router_w.float().t()

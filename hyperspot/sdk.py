@@ -203,6 +203,12 @@ class HyperspotClient:
     def chat(self, messages: List[Dict[str, Any]],
              model: Optional[str] = None,
              **params: Any) -> Dict[str, Any]:
+        """One blocking chat completion.  `params` are the request's
+        sampling fields as the gateway takes them: temperature, top_p,
+        top_k, max_tokens, seed, logprobs / top_logprobs, and the
+        penalties presence_penalty, frequency_penalty (each in [-2, 2])
+        and repetition_penalty (> 0); a value out of range is a 400
+        validation_error."""
         body = {"model": self._model(model),
                 "messages": self._norm_messages(messages), **params}
         return self.request("POST", "/v1/chat/completions", body)
@@ -232,7 +238,9 @@ class HyperspotClient:
         """Yield every parsed SSE chunk of the stream as a dict: the role
         chunk, one chunk per generated token (`delta.content`, and with
         `logprobs=True` / `top_logprobs=n` a `logprobs.content` list of one
-        entry), then the finish_reason + usage chunk."""
+        entry), then the finish_reason + usage chunk.  `params` as for
+        `chat`, presence_penalty / frequency_penalty / repetition_penalty
+        included; logprob entries describe the penalised distribution."""
         body = {"model": self._model(model),
                 "messages": self._norm_messages(messages),
                 "stream": True, **params}

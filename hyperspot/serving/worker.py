@@ -8,6 +8,12 @@ round-trips).  Speaks newline-delimited JSON over a Unix socket:
   <- {"event":"delta","id":r,"text":t,"token_id":n}
        + "logprob":{"token_id":n,"logprob":x,"top":[[id,lp],...]} when the
          request's params ask: "logprobs": true, "top_logprobs": 0..20
+       params may carry "presence_penalty", "frequency_penalty" (each in
+       [-2, 2]) and "repetition_penalty" (> 0); anything else is answered
+       <- {"event":"error","id":r,"code":"validation_error","message":m}
+       on either protocol.  --device-penalties (EngineConfig.
+       device_penalties, --max-penalty-seqs slots) keeps penalty rows in
+       the pipelined decode; without it they take the synchronous step.
   <- {"event":"done","id":r,"finish_reason":f,"usage":{...}}
   -> {"type":"abort","id":r}
   -> {"type":"info"}           <- {"event":"info","ready":true,...}
@@ -559,9 +565,19 @@ class MuxChannel:
 def _sampling_params(msg, params, budget):
     """SamplingParams of one chat message (both protocols).  `logprobs`
     (bool) with `top_logprobs` (int, default 0) asks for per-token
-    log-probabilities; the engine refuses values outside 0..20."""
+    log-probabilities; the engine refuses values outside 0..20.  The three
+    penalties are taken as they come (null = absent): _sampling_error
+    answers for what SamplingParams.check_penalties refuses."""
     from hyperspot.engine import SamplingParams
+
+    def pen(name, default):
+        v = params.get(name)
+        return default if v is None else v
+
     return SamplingParams(
+        presence_penalty=pen("presence_penalty", 0.0),
+        frequency_penalty=pen("frequency_penalty", 0.0),
+        repetition_penalty=pen("repetition_penalty", 1.0),
         temperature=float(params.get("temperature", 0.7)),
         top_p=float(params.get("top_p", 1.0)),
         top_k=int(params.get("top_k", 0)),
@@ -579,6 +595,20 @@ def _sampling_params(msg, params, budget):
         logprobs=int(params.get("top_logprobs") or 0)
         if params.get("logprobs") else None,
     )
+
+
+def _sampling_error(sampling):
+    """Message of the validation_error a chat message with these parameters
+    gets (both protocols), or None.  Checked here, on the connection
+    thread: add_request's ValueError would surface in the stepping
+    thread."""
+    if sampling.logprobs is not None and not 0 <= sampling.logprobs <= 20:
+        return "top_logprobs must be in 0..20"
+    try:
+        sampling.check_penalties()
+    except ValueError as e:
+        return str(e).replace("SamplingParams.", "")
+    return None
 
 
 _LP_FLOOR = -9999.0     # JSON has no -inf
@@ -610,10 +640,10 @@ def _mux_chat(msg, state: "WorkerState", mux: "MuxChannel", rids: set):
                       "message": "prompt exceeds context window"})
         return
     sampling = _sampling_params(msg, params, budget)
-    if sampling.logprobs is not None and not 0 <= sampling.logprobs <= 20:
+    err = _sampling_error(sampling)
+    if err is not None:
         mux.send_obj({"event": "error", "id": rid,
-                      "code": "validation_error",
-                      "message": "top_logprobs must be in 0..20"})
+                      "code": "validation_error", "message": err})
         return
     rids.add(rid)
     state.submit_mux(rid, prompt_ids, sampling, mux)
@@ -792,9 +822,10 @@ def _run_chat(msg, state: WorkerState, send):
               "message": "prompt exceeds context window"})
         return
     sampling = _sampling_params(msg, params, budget)
-    if sampling.logprobs is not None and not 0 <= sampling.logprobs <= 20:
+    err = _sampling_error(sampling)
+    if err is not None:
         send({"event": "error", "id": rid, "code": "validation_error",
-              "message": "top_logprobs must be in 0..20"})
+              "message": err})
         return
     q = state.submit(rid, prompt_ids, sampling)
     detok = StreamDetokenizer(state.tokenizer)
@@ -896,6 +927,14 @@ def main():
                     help="compute logprobs at the decode graph's tail, so "
                          "rows that ask for them stay in the pipelined "
                          "decode (EngineConfig.device_logprobs)")
+    ap.add_argument("--device-penalties", action="store_true",
+                    help="apply presence / frequency / repetition penalties "
+                         "in the decode graphs, on device-resident counts, "
+                         "so penalty rows stay in the pipelined decode "
+                         "(EngineConfig.device_penalties)")
+    ap.add_argument("--max-penalty-seqs", type=int, default=256,
+                    help="slots of the penalty count table "
+                         "(EngineConfig.max_penalty_seqs)")
     args = ap.parse_args()
 
     logging.basicConfig(level=logging.INFO,
@@ -917,7 +956,9 @@ def main():
         quant=args.quant, kv_dtype=args.kv_dtype,
         prefill_paged_mfma=args.prefill_paged_mfma,
         device_sampling=args.device_sampling,
-        device_logprobs=args.device_logprobs)
+        device_logprobs=args.device_logprobs,
+        device_penalties=args.device_penalties,
+        max_penalty_seqs=args.max_penalty_seqs)
     rank = 0
     # MoE models shard experts over the same ranks as TP attention
     # (config 4: Mixtral EP over RCCL all-to-all).  Decode graphs stay ON
