@@ -487,6 +487,33 @@ void silu_mul_fp8(torch::Tensor out, torch::Tensor scales, torch::Tensor x) {
 }
 
 
+constexpr long kMoeBM = 256;  // MOE_BM in csrc/moe.hip
+
+// shape contract shared by the bf16 and fp8 grouped GEMMs: x [rows, K],
+// w [E, N, K], out [ntiles*256, N], sorted_ids [ntiles*256]
+void check_moe_gemm_shapes(const torch::Tensor& out, const torch::Tensor& x,
+                           const torch::Tensor& w,
+                           const torch::Tensor& sorted_ids,
+                           const torch::Tensor& tile_expert,
+                           long gather_div, const char* op) {
+  const long P = tile_expert.numel() * kMoeBM;
+  TORCH_CHECK(w.dim() == 3, op, ": w must be [E, N, K]");
+  TORCH_CHECK(gather_div >= 0, op, ": gather_div must be >= 0");
+  TORCH_CHECK(out.dim() == 2 && out.size(0) == P &&
+                  out.size(1) == w.size(1),
+              op, ": out must be [ntiles*256, N]");
+  TORCH_CHECK(sorted_ids.numel() == P, op,
+              ": sorted_ids must hold ntiles*256 entries");
+  TORCH_CHECK(x.dim() == 2 && x.size(1) == w.size(2), op,
+              ": x must be [rows, K]");
+  if (gather_div == 0) {
+    TORCH_CHECK(x.size(0) == P, op,
+                ": plain mode needs x with ntiles*256 rows");
+  } else {  // pad rows stage row 0 of x
+    TORCH_CHECK(x.size(0) >= 1, op, ": gather mode needs a non-empty x");
+  }
+}
+
 void moe_align(torch::Tensor sorted_ids, torch::Tensor tile_expert,
                torch::Tensor inv_pos, torch::Tensor flat_ids,
                long num_experts) {
@@ -494,6 +521,17 @@ void moe_align(torch::Tensor sorted_ids, torch::Tensor tile_expert,
   check(tile_expert, torch::kInt, "tile_expert");
   check(inv_pos, torch::kInt, "inv_pos");
   check(flat_ids, torch::kInt, "flat_ids");
+  // everything the kernel (and the GEMMs after it) will use as an index
+  // bound is settled here, on the host, without a sync
+  TORCH_CHECK(num_experts >= 1 && num_experts <= 64,
+              "moe_align: num_experts must be in [1, 64]");
+  TORCH_CHECK(sorted_ids.numel() == tile_expert.numel() * kMoeBM,
+              "moe_align: sorted_ids must hold ntiles*256 entries");
+  TORCH_CHECK(tile_expert.numel() * kMoeBM >=
+                  flat_ids.numel() + num_experts * (kMoeBM - 1),
+              "moe_align: ntiles cannot hold the worst-case padded length");
+  TORCH_CHECK(inv_pos.numel() == flat_ids.numel(),
+              "moe_align: inv_pos must hold one entry per pair");
   launch_moe_align(sorted_ids.data_ptr<int>(), tile_expert.data_ptr<int>(),
                    inv_pos.data_ptr<int>(), flat_ids.data_ptr<int>(),
                    (int)flat_ids.numel(), (int)num_experts,
@@ -509,7 +547,8 @@ void moe_gemm(torch::Tensor out, torch::Tensor x, torch::Tensor w,
   check(w, torch::kBFloat16, "w");
   check(sorted_ids, torch::kInt, "sorted_ids");
   check(tile_expert, torch::kInt, "tile_expert");
-  TORCH_CHECK(w.dim() == 3, "w must be [E, N, K]");
+  check_moe_gemm_shapes(out, x, w, sorted_ids, tile_expert, gather_div,
+                        "moe_gemm");
   float* wsp = nullptr;
   if (splitk > 1) {
     TORCH_CHECK(ws.has_value(), "moe_gemm: splitk>1 needs a workspace");
@@ -531,6 +570,13 @@ void moe_combine(torch::Tensor out, torch::Tensor y, torch::Tensor wts,
   check(y, torch::kBFloat16, "y");
   check(wts, torch::kFloat, "wts");
   check(inv_pos, torch::kInt, "inv_pos");
+  TORCH_CHECK(topk >= 1, "moe_combine: topk must be >= 1");
+  TORCH_CHECK(out.dim() == 2 && y.dim() == 2 && y.size(1) == out.size(1),
+              "moe_combine: y and out must share the hidden size");
+  TORCH_CHECK(wts.numel() == out.size(0) * topk &&
+                  inv_pos.numel() == out.size(0) * topk,
+              "moe_combine: wts and inv_pos must hold T*topk entries");
+  if (out.size(0) == 0) return;  // a rank that received nothing: no grid
   launch_moe_combine(bf(out), cbf(y), wts.data_ptr<float>(),
                      inv_pos.data_ptr<int>(), out.size(0), (int)topk,
                      (int)out.size(-1), stream());
@@ -549,7 +595,12 @@ void moe_gemm_fp8(torch::Tensor out, torch::Tensor xq, torch::Tensor xs,
   check(ws, torch::kFloat, "ws");
   check(sorted_ids, torch::kInt, "sorted_ids");
   check(tile_expert, torch::kInt, "tile_expert");
-  TORCH_CHECK(wq.dim() == 3, "wq must be [E, N, K]");
+  check_moe_gemm_shapes(out, xq, wq, sorted_ids, tile_expert, gather_div,
+                        "moe_gemm_fp8");
+  TORCH_CHECK(xs.numel() == xq.size(0),
+              "moe_gemm_fp8: xs must hold one scale per row of xq");
+  TORCH_CHECK(ws.numel() == wq.size(0) * wq.size(1),
+              "moe_gemm_fp8: ws must hold E*N scales");
   float* skp = nullptr;
   if (splitk > 1) {
     TORCH_CHECK(skw.has_value(),

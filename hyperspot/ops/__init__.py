@@ -284,8 +284,15 @@ def moe_ffn(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor,
     the two grouped MFMA GEMMs and the weighted combine all run on-device
     with grids that depend only on (T, K, E) — no host sync, no dynamic
     shapes (MoE dispatch/combine + grouped GEMM).
+
+    Every id must lie in [0, E_local): the kernels index LDS counters and
+    the weight tensor with it, and checking that would take a host sync,
+    so ids outside the range are outside the contract.  T == 0 (an EP rank
+    that received nothing) returns an empty [0, H] tensor, no launch.
     """
     T, H = x.shape
+    if T == 0:
+        return torch.empty(0, H, dtype=torch.bfloat16, device=x.device)
     K = ids.shape[1]
     E = w13.shape[0]
     TK = T * K
@@ -319,8 +326,15 @@ def moe_ffn_fp8(xq: "QTensor", w13q: torch.Tensor, w13s: torch.Tensor,
     norm producer) x e4m3fn expert weights through
     v_mfma_f32_32x32x16_fp8_fp8; the silu stage re-quantizes via the fused
     silu_mul_fp8 kernel so no extra passes appear.  ~2x the bf16 MoE
-    weight bandwidth (the binding constraint, profiles/r01)."""
+    weight bandwidth (the binding constraint, profiles/r01).
+
+    As for moe_ffn, ids outside [0, E_local) are outside the contract (no
+    check without a host sync), and T == 0 returns an empty [0, H] tensor
+    without a launch."""
     T, H = xq.data.shape
+    if T == 0:
+        return torch.empty(0, H, dtype=torch.bfloat16,
+                           device=xq.data.device)
     K = ids.shape[1]
     E = w13q.shape[0]
     TK = T * K
