@@ -63,6 +63,9 @@ void launch_penalty_apply(bf16*, const int*, const float*, const float*,
                           hipStream_t);
 void launch_penalty_note(int*, const int*, const long*, long, int, int,
                          hipStream_t);
+int guided_words();
+void launch_guided_json_mask(bf16*, const int*, long, int, hipStream_t);
+void launch_guided_json_advance(int*, const long*, long, hipStream_t);
 
 namespace {
 
@@ -443,6 +446,49 @@ void penalty_note(torch::Tensor table, torch::Tensor slot,
                       (int)table.size(1), stream());
 }
 
+// JSON-mode guided decoding (csrc/guided.hip): state int32 [rows, words],
+// word 0 < 0 = not a guided row.
+void check_guided_state(const torch::Tensor& state) {
+  check(state, torch::kInt32, "state");
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == guided_words(),
+              "state must be int32 [rows, ", guided_words(), "]");
+}
+
+// In place on logits [rows, vocab]: -inf on every token a guided row's state
+// does not allow; rows with state[r, 0] < 0 are left alone.
+void guided_json_mask(torch::Tensor logits, torch::Tensor state) {
+  check(logits, torch::kBFloat16, "logits");
+  check_guided_state(state);
+  TORCH_CHECK(logits.dim() == 2, "logits must be [rows, vocab]");
+  TORCH_CHECK(logits.size(1) >= 260,
+              "guided_json_mask: the vocabulary must hold the 260 ids of "
+              "the byte tokenizer, got ", logits.size(1));
+  const int64_t rows = logits.size(0);
+  TORCH_CHECK(logits.size(1) < (1LL << 31) - 8192 &&
+                  rows * (logits.size(1) / 8192 + 2) < (1LL << 31),
+              "rows * vocab too large");
+  TORCH_CHECK(state.size(0) >= rows,
+              "state must have at least `rows` rows");
+  TORCH_CHECK(state.device() == logits.device(),
+              "guided_json_mask: tensors on different devices");
+  launch_guided_json_mask(bf(logits), state.data_ptr<int>(), rows,
+                          (int)logits.size(1), stream());
+}
+
+// state[r] := state[r] fed sampled[r], for the first `rows` = sampled.numel()
+// rows that are guided; tokens outside 4..259 are ignored.
+void guided_json_advance(torch::Tensor state, torch::Tensor sampled) {
+  check_guided_state(state);
+  check(sampled, torch::kInt64, "sampled");
+  const int64_t rows = sampled.numel();
+  TORCH_CHECK(state.size(0) >= rows && rows < (1LL << 31),
+              "state must have at least `rows` rows");
+  TORCH_CHECK(sampled.device() == state.device(),
+              "guided_json_advance: tensors on different devices");
+  launch_guided_json_advance(state.data_ptr<int>(),
+                             sampled.data_ptr<long>(), rows, stream());
+}
+
 }  // namespace
 
 
@@ -642,4 +688,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("penalty_build", &penalty_build);
   m.def("penalty_apply", &penalty_apply);
   m.def("penalty_note", &penalty_note);
+  m.def("guided_json_mask", &guided_json_mask);
+  m.def("guided_json_advance", &guided_json_advance);
 }

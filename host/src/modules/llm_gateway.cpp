@@ -638,6 +638,8 @@ void LlmGatewayModule::spawn_one(Worker& wk) {
         args.push_back("--device-logprobs");
       if (worker_cfg_.at("device_penalties").as_bool(false))
         args.push_back("--device-penalties");
+      if (worker_cfg_.at("device_guided").as_bool(false))
+        args.push_back("--device-guided");
     }
     std::vector<char*> argv;
     for (auto& a : args) argv.push_back(const_cast<char*>(a.c_str()));

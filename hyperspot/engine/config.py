@@ -151,6 +151,16 @@ class EngineConfig:
     # the synchronous step, and the table is allocated at the first one
     device_penalties: bool = False
     max_penalty_seqs: int = 256          # slots of the penalty count table
+    # keep JSON-mode rows (SamplingParams.response_format="json", no
+    # response_schema) in the pipelined decode: every decode graph then runs
+    # ops.guided_json_mask in front of the sampler and
+    # ops.guided_json_advance behind it, on an automaton state int32
+    # [rows, 11] per graph.  The device stack holds 256 levels: at that depth
+    # '{' and '[' are masked, where the host machine nests without bound.
+    # Off by default, so that the default graphs launch what they always
+    # did; JSON rows then take the synchronous step, as schema and tool-call
+    # rows do either way
+    device_guided: bool = False
     seed: int = 0
     # decode hipGraph capture batch buckets (padded up to nearest)
     graph_batch_sizes: tuple = (1, 2, 4, 8, 16, 24, 32, 48, 64, 96, 128,

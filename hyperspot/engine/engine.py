@@ -106,24 +106,31 @@ class LLMEngine:
     # ---- pipelined stepping (depth one) ----
 
     def _pipe_eligible(self) -> bool:
-        """Every running row unguided, greedy unless the device samples
+        """Every running row unguided unless it is in plain JSON mode and
+        the decode graphs run that grammar (EngineConfig.device_guided;
+        schema and tool-call rows never, nor a machine nested deeper than
+        the device state holds), greedy unless the device samples
         (EngineConfig.device_sampling), without logprobs unless the
         decode graphs compute them (EngineConfig.device_logprobs), and
         without penalties unless the graphs apply them and keep the counts
         (EngineConfig.device_penalties; at most max_penalty_seqs such
         rows): the next decode step's inputs then depend on the in-flight
-        tokens only through input_ids and those counts, which the device
-        already holds."""
+        tokens only through input_ids, those counts and the grammar state,
+        which the device already holds."""
         stochastic_ok = self.config.device_sampling
         logprobs_ok = self.config.device_logprobs
         penalties_ok = self.config.device_penalties
+        guided_ok = self.config.device_guided
         npen = 0
         for r in self.scheduler.running:
             sp = r.sampling
             if (sp.temperature != 0 and not stochastic_ok) \
                     or (sp.logprobs is not None and not logprobs_ok) \
                     or sp.response_schema is not None \
-                    or sp.response_format in ("json", "tool_call"):
+                    or sp.response_format == "tool_call":
+                return False
+            if sp.response_format == "json" and not (
+                    guided_ok and self.runner.guided_fits_device(r)):
                 return False
             if sp.penalized:
                 npen += 1
@@ -134,8 +141,9 @@ class LLMEngine:
     def step_pipelined(self) -> List[StepOutput]:
         """Enqueue decode step n+1, then wait for and return the outputs
         of step n ([] while the pipeline fills).  Whatever the fast path
-        does not cover (a prefill, a stochastic or guided row, preemption,
-        tensor parallelism) first drains, then takes step().  A row that
+        does not cover (a prefill, a stochastic or guided row without its
+        device flag, preemption, tensor parallelism) first drains, then
+        takes step().  A row that
         reaches max_tokens in the in-flight step is left out of the next
         one; EOS / stop tokens are seen one step late, and the token of
         that extra step is dropped, so streams and finish reasons are

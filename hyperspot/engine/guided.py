@@ -10,7 +10,9 @@ BYTES may come next, and the sampler masks every other token id, so a
 JSON and can only stop (EOS) once the top-level value is closed.
 
 Engine integration: model_runner._apply_guided (mask), worker maps
-`response_schema`/`response_format` from the chat request.
+`response_schema`/`response_format` from the chat request.  With
+EngineConfig.device_guided the JSON machine also runs on the device
+(csrc/guided.hip) from the state that JsonByteMachine.pack() gives.
 """
 
 from __future__ import annotations
@@ -208,6 +210,59 @@ class JsonByteMachine:
         self.consumed += 1
         if 4 <= token_id < 4 + 256:
             self.feed(token_id - 4)
+
+    # ---- device state (csrc/guided.hip spells the layout out) ----
+
+    def pack(self) -> List[int]:
+        """The machine as one row of the device state: GUIDED_WORDS int32
+        values (ops/torch_ref.py).  `consumed` is host bookkeeping and is
+        not part of it.  A stack deeper than the device's 256 levels does
+        not fit (ValueError): the engine keeps such a row off the device."""
+        from hyperspot.ops import torch_ref as tr
+        depth = len(self.stack)
+        if depth > tr.GUIDED_MAX_DEPTH:
+            raise ValueError(f"stack depth {depth} exceeds the device "
+                             f"state's {tr.GUIDED_MAX_DEPTH}")
+        lit = bytes(self.lit)
+        which = 0
+        if lit:
+            which = next(i for i in (1, 2, 3)
+                         if tr.GUIDED_LITS[i].endswith(lit))
+        bits = 0
+        for d, c in enumerate(self.stack):
+            if c == "obj":
+                bits |= 1 << d
+        words = [tr.GUIDED_MODES.index(self.mode),
+                 int(self.in_key) | (self.hex_left << 1) | (which << 4)
+                 | (len(lit) << 6),
+                 depth]
+        for k in range(tr.GUIDED_WORDS - 3):
+            w = (bits >> (32 * k)) & 0xFFFFFFFF
+            words.append(w - (1 << 32) if w >= (1 << 31) else w)
+        return words
+
+    @classmethod
+    def unpack(cls, words) -> "JsonByteMachine":
+        """The machine that pack() made `words` from (consumed = 0).  The
+        device's DEAD mode has no host counterpart: ValueError."""
+        from hyperspot.ops import torch_ref as tr
+        words = [int(w) for w in words]
+        if len(words) != tr.GUIDED_WORDS \
+                or not 0 <= words[0] < len(tr.GUIDED_MODES) \
+                or not 0 <= words[2] <= tr.GUIDED_MAX_DEPTH:
+            raise ValueError(f"not a packed JsonByteMachine: {words!r}")
+        m = cls()
+        m.mode = tr.GUIDED_MODES[words[0]]
+        f = words[1]
+        m.in_key = bool(f & 1)
+        m.hex_left = (f >> 1) & 7
+        which, n = (f >> 4) & 3, (f >> 6) & 7
+        m.lit = tr.GUIDED_LITS[which][len(tr.GUIDED_LITS[which]) - n:] \
+            if n else b""
+        m.stack = [
+            "obj" if (words[3 + (d >> 5)] >> (d & 31)) & 1 else "arr"
+            for d in range(words[2])]
+        return m
 
 
 class ToolCallMachine:

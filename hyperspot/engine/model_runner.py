@@ -384,6 +384,8 @@ class ModelRunner:
                 io["lp_n"].fill_(-1)          # and computes no logprobs
             if self.config.device_penalties:
                 io["pen_slot"].fill_(-1)      # and penalises no row
+            if self.config.device_guided:
+                io["gd_state"].fill_(-1)      # and masks none
             io["passthrough"] = True
         io["input_ids"][:B] = input_ids
         io["input_ids"][B:] = 0
@@ -500,6 +502,12 @@ class ModelRunner:
             io["pen_rep"] = torch.ones(rows, dtype=torch.float32, device=d)
             io["pen_pres"] = torch.zeros(rows, dtype=torch.float32, device=d)
             io["pen_freq"] = torch.zeros(rows, dtype=torch.float32, device=d)
+        if self.config.device_guided:
+            # word 0 = -1 = not a guided row: padding rows, pass-through
+            # replays, rows that are not in JSON mode
+            io["gd_state"] = torch.full(
+                (rows, ops.torch_ref.GUIDED_WORDS), -1, dtype=torch.int32,
+                device=d)
         if not self.config.device_sampling:
             io["ctl"] = torch.full((4 * rows + 4,), -1, dtype=torch.int32,
                                    device=d)
@@ -524,11 +532,21 @@ class ModelRunner:
             ops.penalty_apply(logits, io["pen_slot"], io["pen_rep"],
                               io["pen_pres"], io["pen_freq"],
                               self._pen_table)
+        guided = self.config.device_guided
+        if guided:
+            # behind the penalties and in front of the sampler, the order of
+            # _sample: the logprobs describe the masked logits
+            ops.guided_json_mask(logits, io["gd_state"])
         if self.config.device_sampling:
             ops.sample_fused(logits, io["temperature"], io["top_p"],
                              io["top_k"], io["uniform"], out=io["sampled"])
         else:
             ops.greedy_sample(logits, out=io["sampled"])
+        if guided:
+            # the next step's mask is that of the state behind this token.
+            # EOS is no byte and leaves the state alone, so the extra step of
+            # a row whose EOS is seen one step late is masked like the last
+            ops.guided_json_advance(io["gd_state"], io["sampled"])
         if pen:
             # the next step's penalty_apply counts this token.  A row that
             # runs a step past its end (EOS seen one step late, dropped,
@@ -627,6 +645,8 @@ class ModelRunner:
             self._pipe["lp_n"] = lp[:B].numpy()
         if self.config.device_penalties:
             self._pipe_seed_penalties(reqs, io, nrows)
+        if self.config.device_guided:
+            self._pipe_seed_guided(reqs, io, nrows)
 
     def _pipe_seed_penalties(self, reqs: List[Request], io: dict,
                              nrows: int) -> None:
@@ -831,6 +851,59 @@ class ModelRunner:
 
     # ---------------- sampling ----------------
 
+    def _guided_machine(self, r: Request):
+        """The request's grammar machine, created on first use and fed
+        every output token it has not seen yet.  Shared by the host mask
+        (_apply_guided) and the device state's re-seed (_pipe_seed_guided),
+        so both stand on the same machine.  After a preemption has folded
+        the outputs into the prompt the machine has consumed more than
+        output_token_ids holds and a fresh one takes its place."""
+        from .guided import (JsonByteMachine, SchemaMachine,
+                             ToolCallMachine)
+        m = getattr(r, "_guided", None)
+        if m is None or m.consumed > len(r.output_token_ids):
+            if r.sampling.response_format == "tool_call":
+                m = ToolCallMachine(tuple(r.sampling.tool_names))
+            elif r.sampling.response_schema is not None:
+                try:
+                    # untrusted schema: any compile failure degrades
+                    # to plain JSON-grammar enforcement
+                    m = SchemaMachine(r.sampling.response_schema)
+                except Exception:
+                    m = JsonByteMachine()
+            else:
+                m = JsonByteMachine()
+            r._guided = m
+        for t in r.output_token_ids[m.consumed:]:
+            m.feed_token(t)
+        return m
+
+    def guided_fits_device(self, r: Request) -> bool:
+        """A JSON-mode row whose machine, caught up with its outputs, fits
+        the device state's 256-level stack (LLMEngine._pipe_eligible asks
+        with nothing in flight, so the outputs are complete)."""
+        m = self._guided_machine(r)
+        return len(m.stack) <= ops.torch_ref.GUIDED_MAX_DEPTH
+
+    def _pipe_seed_guided(self, reqs: List[Request], io: dict,
+                          nrows: int) -> None:
+        """Upload the automaton state of the JSON-mode rows (once per
+        re-seed; every other row is -1).  Nothing is in flight at a
+        re-seed, so the host machine has been fed every output token, the
+        last one included: that one goes into this step through
+        decode_advance's host-id path, and guided_json_advance only ever
+        sees newly sampled tokens.  Nothing comes back from the device: the
+        host machine catches up from output_token_ids at the next
+        synchronous step or re-seed."""
+        st = torch.full((nrows, ops.torch_ref.GUIDED_WORDS), -1,
+                        dtype=torch.int32)
+        for i, r in enumerate(reqs):
+            if r.sampling.response_format == "json" \
+                    and r.sampling.response_schema is None:
+                st[i] = torch.tensor(self._guided_machine(r).pack(),
+                                     dtype=torch.int32)
+        io["gd_state"].copy_(st)
+
     def _apply_guided(self, logits: torch.Tensor,
                       requests: List[Request]) -> None:
         """Structured-output mask (SamplingParams.response_format="json"):
@@ -842,30 +915,13 @@ class ModelRunner:
                or r.sampling.response_schema is not None]
         if not gis:
             return
-        from .guided import (JsonByteMachine, SchemaMachine,
-                             ToolCallMachine)
         NB = 4 + 256                       # specials + byte ids
         neg = float("-inf")
         rows: List[torch.Tensor] = []
         cache = self._guided_mask_cache
         for k, i in enumerate(gis):
             r = requests[i]
-            m = getattr(r, "_guided", None)
-            if m is None or m.consumed > len(r.output_token_ids):
-                if r.sampling.response_format == "tool_call":
-                    m = ToolCallMachine(tuple(r.sampling.tool_names))
-                elif r.sampling.response_schema is not None:
-                    try:
-                        # untrusted schema: any compile failure degrades
-                        # to plain JSON-grammar enforcement
-                        m = SchemaMachine(r.sampling.response_schema)
-                    except Exception:
-                        m = JsonByteMachine()
-                else:
-                    m = JsonByteMachine()
-                r._guided = m
-            for t in r.output_token_ids[m.consumed:]:
-                m.feed_token(t)
+            m = self._guided_machine(r)
             # cache mask rows by machine state (mask_key): avoids a
             # ~230-iteration Python loop per guided sequence per step
             key = m.mask_key() if hasattr(m, "mask_key") else None

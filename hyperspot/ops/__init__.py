@@ -485,6 +485,39 @@ def penalty_note(table: torch.Tensor, slot: torch.Tensor,
     torch_ref.penalty_note(table, slot, sampled)
 
 
+def guided_json_mask(logits: torch.Tensor, state: torch.Tensor) -> None:
+    """JSON-mode grammar mask in place on logits [rows, vocab], from the
+    per-row automaton state (csrc/guided.hip).
+
+    state int32 [at least rows, torch_ref.GUIDED_WORDS], read on the device,
+    so the launch depends on rows and vocab alone and can be captured.
+    state[r, 0] < 0 = not a guided row, left untouched; in a guided row every
+    token the state does not allow becomes -inf and the others keep their
+    bits.  A vocabulary below the byte tokenizer's 260 ids is refused.
+    torch_ref.guided_json_mask spells the semantics out.  bf16 GPU logits go
+    to the kernel, anything else to the torch twin."""
+    if logits.shape[-1] < torch_ref.GUIDED_BYTE_IDS:
+        raise ValueError(
+            f"guided_json_mask: the vocabulary must hold the "
+            f"{torch_ref.GUIDED_BYTE_IDS} ids of the byte tokenizer, got "
+            f"{logits.shape[-1]}")
+    if logits.is_cuda and logits.dtype == torch.bfloat16:
+        _native().guided_json_mask(logits, state)
+        return
+    torch_ref.guided_json_mask(logits, state)
+
+
+def guided_json_advance(state: torch.Tensor, sampled: torch.Tensor) -> None:
+    """Feed each guided row the token it has just sampled: state[r] :=
+    state[r] after byte sampled[r] - 4, for r < len(sampled) with
+    state[r, 0] >= 0 (csrc/guided.hip).  Tokens outside 4..259 are ignored.
+    sampled int64 [rows]; capturable."""
+    if state.is_cuda:
+        _native().guided_json_advance(state, sampled)
+        return
+    torch_ref.guided_json_advance(state, sampled)
+
+
 def decode_advance(input_ids: torch.Tensor, positions: torch.Tensor,
                    seq_lens: torch.Tensor, slot_mapping: torch.Tensor,
                    block_tables: torch.Tensor, sampled_prev: torch.Tensor,

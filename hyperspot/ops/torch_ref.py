@@ -419,6 +419,254 @@ def penalty_note(table: torch.Tensor, slot: torch.Tensor,
                                 device=table.device), accumulate=True)
 
 
+# JSON-mode guided decoding on the device (csrc/guided.hip spells the state
+# layout out).  A state row is GUIDED_WORDS int32 words: mode | flags | depth
+# | 8 words of stack bits; the mode numbers index GUIDED_MODES, the modes of
+# engine.guided.JsonByteMachine in the order of its allowed(), and GUIDED_DEAD
+# follows them.
+GUIDED_WORDS = 11
+GUIDED_MODES = ("value", "value_first", "key", "key_first", "colon", "string",
+                "escape", "hex", "lit", "num_minus", "num_zero", "num_int",
+                "num_dot", "num_frac", "num_esign", "num_e", "num_exp", "end")
+GUIDED_DEAD = len(GUIDED_MODES)         # 18: allows EOS only, sticky
+GUIDED_MAX_DEPTH = 256                  # no '{' or '[' at this depth
+GUIDED_BYTE_IDS = 4 + 256               # byte b is id b + 4, EOS is id 2
+# the literals' bytes after the first, by literal number 1..3; a remaining
+# b"e" is stored as number 1 whichever literal it ends
+GUIDED_LITS = (b"", b"rue", b"alse", b"ull")
+
+_G = {m: i for i, m in enumerate(GUIDED_MODES)}
+_G_DIGITS = frozenset(b"0123456789")
+_G_HEX = frozenset(b"0123456789abcdefABCDEF")
+_G_ESC = frozenset(b'"\\/bfnrtu')
+_G_EXP = frozenset(b"eE")
+_G_TERMINABLE = (_G["num_zero"], _G["num_int"], _G["num_frac"], _G["num_exp"],
+                 _G["end"])
+
+
+def _guided_load(w):
+    """(mode, in_key, hex_left, lit, lit_n, depth, top) of one state row
+    (a list of ints, w[0] >= 0); top -1 = stack empty, 0 arr, 1 obj.  Words
+    out of range read as GUIDED_DEAD, as in the kernels."""
+    mode, f, depth = w[0], w[1], w[2]
+    in_key, hex_left = f & 1, (f >> 1) & 7
+    lit, lit_n = (f >> 4) & 3, (f >> 6) & 7
+    if mode > GUIDED_DEAD or depth < 0 or depth > GUIDED_MAX_DEPTH:
+        mode, depth = GUIDED_DEAD, 0
+    if mode == _G["lit"] and (lit == 0 or lit_n < 1
+                              or lit_n > len(GUIDED_LITS[lit])):
+        mode = GUIDED_DEAD
+    top = -1
+    if depth > 0:
+        d = depth - 1
+        top = (w[3 + (d >> 5)] >> (d & 31)) & 1
+    return mode, in_key, hex_left, lit, lit_n, depth, top
+
+
+def _guided_allowed(mode: int, lit: int, lit_n: int, depth: int, top: int):
+    """(frozenset of allowed bytes, eos_ok) of a loaded state."""
+    end = frozenset() if top < 0 else frozenset(b",}" if top else b",]")
+    start = set(b'"-tfn') | _G_DIGITS
+    if depth < GUIDED_MAX_DEPTH:
+        start |= set(b"{[")
+    eos = top < 0 and mode in _G_TERMINABLE
+    m = GUIDED_MODES[mode] if mode < GUIDED_DEAD else "DEAD"
+    if m == "value":
+        ok = start
+    elif m == "value_first":
+        ok = start | (set(b"]") if top >= 0 else set())
+    elif m == "key":
+        ok = set(b'"')
+    elif m == "key_first":
+        ok = set(b'"') | (set(b"}") if top >= 0 else set())
+    elif m == "colon":
+        ok = set(b":")
+    elif m == "string":
+        ok = set(range(0x20, 0x100))
+    elif m == "escape":
+        ok = _G_ESC
+    elif m == "hex":
+        ok = _G_HEX
+    elif m == "lit":
+        tail = GUIDED_LITS[lit]
+        ok = {tail[len(tail) - lit_n]}
+    elif m in ("num_minus", "num_dot", "num_esign"):
+        ok = _G_DIGITS
+    elif m == "num_zero":
+        ok = set(b".") | _G_EXP | end
+    elif m == "num_int":
+        ok = _G_DIGITS | set(b".") | _G_EXP | end
+    elif m == "num_frac":
+        ok = _G_DIGITS | _G_EXP | end
+    elif m == "num_e":
+        ok = _G_DIGITS | set(b"+-")
+    elif m == "num_exp":
+        ok = _G_DIGITS | end
+    elif m == "end":
+        ok = end
+    else:                               # DEAD: may only stop
+        ok, eos = set(), True
+    return frozenset(ok), eos
+
+
+def guided_json_mask(logits: torch.Tensor, state: torch.Tensor) -> None:
+    """Twin of csrc/guided.hip guided_json_mask, in place on logits [R, V]
+    (V >= 260).  For the rows r < R with state[r, 0] >= 0 every token id the
+    row's state does not allow becomes -inf: ids >= 260, ids 0, 1 and 3,
+    id 2 (EOS) unless the top-level value is closed, id 4 + b unless byte b
+    may come next.  Allowed logits, and the other rows, keep their bits."""
+    R, V = logits.shape
+    if V < GUIDED_BYTE_IDS:
+        raise ValueError(
+            f"guided_json_mask: the vocabulary must hold the "
+            f"{GUIDED_BYTE_IDS} ids of the byte tokenizer, got {V}")
+    st = state[:R].cpu()
+    rows = torch.nonzero(st[:, 0] >= 0).flatten().tolist()
+    if not rows:
+        return
+    keep = torch.zeros(len(rows), V, dtype=torch.bool)
+    for k, r in enumerate(rows):
+        mode, _, _, lit, lit_n, depth, top = _guided_load(st[r].tolist())
+        ok, eos = _guided_allowed(mode, lit, lit_n, depth, top)
+        if ok:
+            keep[k, torch.tensor(sorted(ok)) + 4] = True
+        keep[k, 2] = eos
+    idx = torch.tensor(rows, device=logits.device)
+    old = logits[idx]
+    logits[idx] = torch.where(keep.to(logits.device), old,
+                              torch.full_like(old, float("-inf")))
+
+
+def _guided_feed(w, b: int) -> None:
+    """One state row (a list of ints, w[0] >= 0) fed byte b, in place: the
+    port of JsonByteMachine.feed that the advance kernel runs."""
+    mode, in_key, hex_left, lit, lit_n, depth, top = _guided_load(w)
+    ok, _ = _guided_allowed(mode, lit, lit_n, depth, top)
+    if b not in ok:
+        w[0] = GUIDED_DEAD
+        return
+
+    def push(obj):
+        nonlocal depth
+        if obj:
+            w[3 + (depth >> 5)] |= 1 << (depth & 31)
+        depth += 1
+
+    def pop():
+        nonlocal depth
+        depth -= 1
+        w[3 + (depth >> 5)] &= ~(1 << (depth & 31))
+
+    def feed_end():
+        if b == ord(","):
+            return _G["key"] if top else _G["value"]
+        pop()
+        return _G["end"]
+
+    m = GUIDED_MODES[mode]
+    digit = b in _G_DIGITS
+    if m in ("value", "value_first"):
+        if m == "value_first" and b == ord("]"):
+            pop()
+            m = "end"
+        elif b == ord('"'):
+            in_key, m = 0, "string"
+        elif b == ord("{"):
+            push(1)
+            m = "key_first"
+        elif b == ord("["):
+            push(0)
+            m = "value_first"
+        elif b == ord("-"):
+            m = "num_minus"
+        elif b == ord("0"):
+            m = "num_zero"
+        elif digit:
+            m = "num_int"
+        else:
+            lit = 1 if b == ord("t") else 2 if b == ord("f") else 3
+            lit_n = len(GUIDED_LITS[lit])
+            m = "lit"
+    elif m in ("key", "key_first"):
+        if b == ord("}"):
+            pop()
+            m = "end"
+        else:
+            in_key, m = 1, "string"
+    elif m == "colon":
+        m = "value"
+    elif m == "string":
+        if b == 0x22:
+            m = "colon" if in_key else "end"
+        elif b == 0x5C:
+            m = "escape"
+    elif m == "escape":
+        if b == ord("u"):
+            hex_left, m = 4, "hex"
+        else:
+            m = "string"
+    elif m == "hex":
+        hex_left -= 1
+        if hex_left <= 0:
+            hex_left, m = 0, "string"
+    elif m == "lit":
+        lit_n -= 1
+        if lit_n == 0:
+            lit, m = 0, "end"
+        elif lit_n == 1 and lit == 2:
+            lit = 1
+    elif m == "num_minus":
+        m = "num_zero" if b == ord("0") else "num_int"
+    elif m in ("num_zero", "num_int", "num_frac", "num_exp"):
+        if b == ord("."):
+            m = "num_dot"
+        elif b in _G_EXP and m != "num_exp":
+            m = "num_e"
+        elif digit and m != "num_zero":
+            pass
+        else:
+            m = GUIDED_MODES[feed_end()]
+    elif m == "num_dot":
+        m = "num_frac"
+    elif m == "num_e":
+        m = "num_exp" if digit else "num_esign"
+    elif m == "num_esign":
+        m = "num_exp"
+    else:                               # end
+        m = GUIDED_MODES[feed_end()]
+    w[0] = _G[m]
+    w[1] = in_key | (hex_left << 1) | (lit << 4) | (lit_n << 6)
+    w[2] = depth
+
+
+def _guided_i32(x: int) -> int:
+    """Python int -> the int32 with the same low 32 bits."""
+    x &= 0xFFFFFFFF
+    return x - (1 << 32) if x >= (1 << 31) else x
+
+
+def guided_json_advance(state: torch.Tensor, sampled: torch.Tensor) -> None:
+    """Twin of guided_json_advance: state[r] := state[r] fed sampled[r] for
+    the rows r < len(sampled) with state[r, 0] >= 0; a token outside 4..259
+    leaves the row as it is (JsonByteMachine.feed_token), a byte the state
+    does not allow makes it GUIDED_DEAD."""
+    R = sampled.numel()
+    st = state[:R].cpu()
+    tok = sampled.cpu().tolist()
+    changed = False
+    for r in torch.nonzero(st[:, 0] >= 0).flatten().tolist():
+        t = tok[r]
+        if t < 4 or t >= GUIDED_BYTE_IDS:
+            continue
+        w = [x & 0xFFFFFFFF if i >= 3 else x
+             for i, x in enumerate(st[r].tolist())]
+        _guided_feed(w, t - 4)
+        st[r] = torch.tensor([_guided_i32(x) for x in w], dtype=torch.int32)
+        changed = True
+    if changed:
+        state[:R] = st.to(state.device)
+
+
 def moe_route(hidden: torch.Tensor, router_w: torch.Tensor, top_k: int):
     """Softmax-topk routing: returns (weights [T,K], expert_ids [T,K])."""
     logits = hidden.float() @ router_w.float().t()

@@ -14,6 +14,10 @@ round-trips).  Speaks newline-delimited JSON over a Unix socket:
        on either protocol.  --device-penalties (EngineConfig.
        device_penalties, --max-penalty-seqs slots) keeps penalty rows in
        the pipelined decode; without it they take the synchronous step.
+       --device-guided (EngineConfig.device_guided) does the same for
+       rows in plain JSON mode ("response_format": "json" without a
+       "response_schema"); schema and tool-call rows take the
+       synchronous step.
   <- {"event":"done","id":r,"finish_reason":f,"usage":{...}}
   -> {"type":"abort","id":r}
   -> {"type":"info"}           <- {"event":"info","ready":true,...}
@@ -935,6 +939,12 @@ def main():
     ap.add_argument("--max-penalty-seqs", type=int, default=256,
                     help="slots of the penalty count table "
                          "(EngineConfig.max_penalty_seqs)")
+    ap.add_argument("--device-guided", action="store_true",
+                    help="run the JSON-mode grammar (response_format "
+                         "json, no response_schema) in the decode graphs, on "
+                         "device-resident automaton state, so such rows "
+                         "stay in the pipelined decode "
+                         "(EngineConfig.device_guided)")
     args = ap.parse_args()
 
     logging.basicConfig(level=logging.INFO,
@@ -958,7 +968,8 @@ def main():
         device_sampling=args.device_sampling,
         device_logprobs=args.device_logprobs,
         device_penalties=args.device_penalties,
-        max_penalty_seqs=args.max_penalty_seqs)
+        max_penalty_seqs=args.max_penalty_seqs,
+        device_guided=args.device_guided)
     rank = 0
     # MoE models shard experts over the same ranks as TP attention
     # (config 4: Mixtral EP over RCCL all-to-all).  Decode graphs stay ON
